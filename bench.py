@@ -14,7 +14,12 @@ over ranks.  Multi-GPU (BASELINE configs[3]): one process per GPU, each rank dec
 independent batches (weak scaling, no data-path collective; an RCCL all_gather of per-rank
 checksums runs once after the timed region).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds, after the timed
+region, what the headline figure does not need: per-batch BER and checksums, the final gather, the side
+measurements (other formats, single launches, float input, channel source, PCIe), the oracle parity block and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step decoded.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
    or: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -298,6 +303,19 @@ def batch_ber(opt, bits, outs, ostride, nout, k, msg):
     dt = np.uint16 if (opt & 0xF00) == vitdec.O_B16 else np.uint32
     out_h = outs[k * ostride: k * ostride + nout].cpu().numpy().view(dt)
     return vitdec.count_errors(opt, bits[k].cpu().numpy(), out_h) / msg, out_h
+
+
+def dump_outputs(dirname, batches, k):
+    """--dump-outputs: the decoded words of batch k (the one the last timed step decoded) of every workload, as
+    the caller of vd_run_device_batch finds them in its output buffer, one DIR/<workload>.npy each: the packed
+    output words (uint32, or uint16 for 16-bit output words) as float64, which holds every word exactly
+    (8 MB per 32M-bit batch).  The inputs come from fixed seeds, so two runs with the same arguments decode the
+    same batches."""
+    os.makedirs(dirname, exist_ok=True)
+    for b in batches:
+        dt = np.uint16 if (b["opt"] & 0xF00) == vitdec.O_B16 else np.uint32
+        words = b["outs"][k * b["ostride"]: k * b["ostride"] + b["nout"]].cpu().numpy().view(dt)
+        np.save(os.path.join(dirname, b["name"] + ".npy"), words.astype(np.float64))
 
 
 def aggregate_gbps(bits_per_step, world, steps, elapsed_s):
@@ -639,6 +657,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--warm-s", type=float, default=WARM_S,
                     help="minimum warm-up in seconds of steps (GPU clock ramp; 0 for counter-collection runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: per-batch BER and "
+                         "checksums, the final gather, the side measurements, the oracle parity block and the CPU "
+                         "baseline (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step decoded (rank 0) as DIR/<workload>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-llr", action="store_true", help="skip the float-input (packer fused) side measurement")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-to-host pipelined side measurement")
@@ -761,13 +785,17 @@ def main():
     # per-launch durations from the HIP events on the launch stream; per batch = / K
     launch_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(nw)]
     kms = [t / K for t in launch_ms]
+    if args.dump_outputs and rank == 0:  # step K - 1 decoded resident batch (K - 1) % P
+        dump_outputs(args.dump_outputs, batches, (K - 1) % P)
+    # everything below that is not the result line's own arithmetic runs with --full only
+    full = args.full
     # correctness side-channel (outside the timed region): the decoded-bit error rate of every batch
     # against its own source bits (max over the resident batches), and per-rank checksums of the decoded
     # words: per workload the xor over every resident batch's words, then the xor of batch 0's words (the
     # batch the final gather collects, which checks what rank 0 received against them)
     bers = []
     sums, sums0 = [], []
-    for b in batches:
+    for b in batches if full else []:
         ber_k, ck = [], 0
         for k in range(P):
             e, out_h = batch_ber(b["opt"], b["bits"], b["outs"], b["ostride"], b["nout"], k, b["msg"])
@@ -779,12 +807,12 @@ def main():
         bers.append(max(ber_k))
         sums.append(ck)
     # side measurements, the kernel-only ones first (the PCIe one leaves the GPU waiting on host copies)
-    side = rank == 0 and metric_run
+    side = rank == 0 and metric_run and full
     # the other formats and the fused float input run in launches of as many batches as the timed region's
     # (at least 20): a shorter launch carries more of the once-per-launch ramp and tail per batch
     side_reps = max(20, P)
     # parity block (rank 0, every N): host copies of the outputs to check against the oracle at the end
-    checks = [] if (rank == 0 and not args.no_parity) else None
+    checks = [] if (rank == 0 and full and not args.no_parity) else None
     if checks is not None:
         for b in batches:
             for k in sorted({0, P - 1}):
@@ -800,10 +828,11 @@ def main():
     pcie = None if (args.no_pcie or not side) else pcie_side_measurement(batches, dev)
     # the same collectives at every N (N = 1: a 1-rank RCCL group)
     elapsed = max_over_ranks(elapsed, cdev)
-    gathered = gather_checksums(sums + sums0, cdev, world)
-    gms, gsums, err = gather_outputs([b["out"].cpu() if REHEARSE else b["out"] for b in batches], cdev, world, rank)
     final_gather = None
-    if rank == 0:
+    if full:
+        gathered = gather_checksums(sums + sums0, cdev, world)
+        gms, gsums, err = gather_outputs([b["out"].cpu() if REHEARSE else b["out"] for b in batches], cdev, world, rank)
+    if full and rank == 0:
         if err is not None:  # a side measurement: report it, keep the bench line
             final_gather = {"error": err}
         else:
@@ -876,8 +905,6 @@ def main():
                 "step_minus_kernels_us": round((ms_per_step - sum(kms)) * 1e3, 2),
                 "warmup_steps_run": nwarm,
                 "kernel_gbps": {b["name"]: round(b["msg"] / (k * 1e-3) / 1e9, 2) for b, k in zip(batches, kms)},
-                "ber": {b["name"]: bers[i] for i, b in enumerate(batches)},
-                "ber_is": "max over the K batches of a launch",
                 "kernels": {b["name"]: b["dec"].kernel_for(b["input_num"], sizes[0], b["llr"]) for b in batches},
             },
             "roofline": {
@@ -908,9 +935,12 @@ def main():
                 },
                 "per_kernel": {b["name"]: rl[i] for i, b in enumerate(batches)},
             },
-            "checksums": [[hex(x) for x in g[:nw]] for g in gathered],
-            "checksums_are": "per rank, per workload: xor of the decoded words over every resident batch",
         }
+        if full:
+            result["config"]["ber"] = {b["name"]: bers[i] for i, b in enumerate(batches)}
+            result["config"]["ber_is"] = "max over the K batches of a launch"
+            result["checksums"] = [[hex(x) for x in g[:nw]] for g in gathered]
+            result["checksums_are"] = "per rank, per workload: xor of the decoded words over every resident batch"
         if llr is not None:
             result["config"]["llr_input"] = llr
         if pcie is not None:
@@ -929,7 +959,7 @@ def main():
             result["config"]["rehearsal"] = "not a measurement: every rank decodes on the same GPU"
         if checks is not None:
             result["config"]["parity"] = parity_block(checks)
-        if not args.no_cpu_baseline and metric_run and world == 1:  # rank 0 at N = 1 only (the bench contract)
+        if full and not args.no_cpu_baseline and metric_run and world == 1:  # rank 0 at N = 1 only (the bench contract)
             result["cpu_baseline"] = cpu_baseline(batches)
         print(json.dumps(result), flush=True)
 

@@ -4,7 +4,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-envab}
 mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-parity --no-llr --no-pcie --no-channel"
+B="python bench.py --full --no-cpu-baseline --no-parity --no-llr --no-pcie --no-channel"
 for r in $(seq 1 ${3:-3}); do
   for v in 1 0; do
     env $2=$v timeout -k 10 240 $B > $O/${v}_$r.log 2>&1 || { echo rc=$? v=$v; tail $O/${v}_$r.log; exit 1; }

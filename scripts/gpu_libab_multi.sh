@@ -7,7 +7,7 @@ O=gpurun_out/${1:-libabm}
 R=${2:-2}
 shift 2
 mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-parity --no-llr --no-pcie --no-channel"
+B="python bench.py --full --no-cpu-baseline --no-parity --no-llr --no-pcie --no-channel"
 for r in $(seq 1 $R); do
   timeout -k 10 240 $B > $O/head_$r.log 2>&1 || { echo head_rc=$?; tail $O/head_$r.log; exit 1; }
   tail -1 $O/head_$r.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('head', {k: v['kernel_ms'] for k, v in d['config']['single_launch'].items()}, d['config']['kernel_ms'])"

@@ -4,7 +4,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-libabs}
 mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-parity --no-llr --no-pcie --no-channel"
+B="python bench.py --full --no-cpu-baseline --no-parity --no-llr --no-pcie --no-channel"
 for r in $(seq 1 ${3:-3}); do
   timeout -k 10 240 $B > $O/new_$r.log 2>&1 || { echo new_rc=$?; tail $O/new_$r.log; exit 1; }
   VITDEC_LIB=$2 timeout -k 10 240 $B > $O/old_$r.log 2>&1 || { echo old_rc=$?; tail $O/old_$r.log; exit 1; }

@@ -6,7 +6,7 @@ O=gpurun_out/${1:-pk1}
 mkdir -p $O
 for r in 1 2; do
   for v in 0 1; do
-    VD_PK_SINGLE=$v timeout -k 10 300 python -u bench.py --no-parity > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err || { echo rc=$? v=$v; tail $O/b_${v}_$r.err; exit 1; }
+    VD_PK_SINGLE=$v timeout -k 10 300 python -u bench.py --full --no-parity > $O/b_${v}_$r.json 2> $O/b_${v}_$r.err || { echo rc=$? v=$v; tail $O/b_${v}_$r.err; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('pk_single=$v', json.dumps(d['config']['single_launch']))" $O/b_${v}_$r.json
   done
 done

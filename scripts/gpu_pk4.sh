@@ -5,7 +5,7 @@ O=gpurun_out/${1:-pk4}
 mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests/test_gpu_pk.py -x -q --timeout 300 --timeout-method thread > $O/tests_pk.log 2>&1 || { echo tests_rc=$?; tail -30 $O/tests_pk.log; exit 1; }
 tail -2 $O/tests_pk.log
-timeout -k 10 300 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo bench_rc=$?; tail $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo bench_rc=$?; tail $O/bench.err; exit 1; }
 python3 -c "
 import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print('value', d['value'], 'kernel_ms', d['config'].get('kernel_ms'))

@@ -5,7 +5,7 @@ O=gpurun_out/${1:-pks}
 mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests/test_gpu_pk.py tests/test_gpu_split.py -x -v --timeout 300 --timeout-method thread > $O/tests.log 2>&1 || { echo tests_rc=$?; grep -E "FAILED|Error|assert" $O/tests.log | head -20; tail -5 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
-timeout -k 10 300 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo bench_rc=$?; tail $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo bench_rc=$?; tail $O/bench.err; exit 1; }
 python3 -c "
 import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print('value', d['value'], 'kernel_ms', d['config'].get('kernel_ms'))

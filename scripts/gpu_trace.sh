@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/${1:-trace}
 mkdir -p $O
-timeout -k 10 420 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py > $O/bench.log 2> $O/bench.err || { echo rc=$?; tail $O/bench.err; exit 1; }
+timeout -k 10 420 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --full > $O/bench.log 2> $O/bench.err || { echo rc=$?; tail $O/bench.err; exit 1; }
 f=$(find $O/trace -name "*kernel_stats.csv" | head -1); cp $f $O/kernel_stats.csv
 t=$(find $O/trace -name "*kernel_trace.csv" | head -1); python3 tools/trace_summary.py $t > $O/kernel_trace_by_grid.txt
 python3 - "$t" > $O/single_launch_gaps.txt <<'PY'

@@ -59,7 +59,7 @@ def test_valu_view_from_committed_pmc():
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--warm-s", "0.05",
-           "--no-cpu-baseline", "--no-llr", "--no-pcie", "--no-channel", "--no-other"]
+           "--full", "--no-cpu-baseline", "--no-llr", "--no-pcie", "--no-channel", "--no-other"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -81,13 +81,55 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert fg["world"] == 1 and fg["checksums_match"] is True, fg
 
 
+def _bench_line(*args):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True,
+                       timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the line holds the headline figure and its roofline, and none of the blocks that take runs
+    or host decodes of their own after the timed region."""
+    d = _bench_line("--gpus", "1", "--steps", "2", "--warmup", "1", "--warm-s", "0.05")
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Gb/s"
+    assert d["higher_is_better"] is True and d["dtype"].startswith("exact integers")
+    assert d["config"]["launch"]["batches_per_launch"] == 2 and d["roofline"]["bound"] == "valu"
+    for k in ("cpu_baseline", "checksums"):
+        assert k not in d, k
+    for k in ("ber", "parity", "final_gather", "other_configs", "single_launch", "llr_input", "pcie_inclusive",
+              "channel_source"):
+        assert k not in d["config"], k
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_steps_words(tmp_path):
+    """--dump-outputs: one float64 array per workload holding the decoded words of the last timed step.  At
+    --steps 1 that is batch 0, whose words the parity block checks against the oracle and whose xor is the
+    line's checksum."""
+    import numpy as np
+    d = _bench_line("--steps", "1", "--warmup", "1", "--warm-s", "0.05", "--full", "--no-cpu-baseline", "--no-llr",
+                    "--no-pcie", "--no-channel", "--no-other", "--dump-outputs", str(tmp_path / "out"))
+    assert d["config"]["parity"]["all_match"] is True, d["config"]["parity"]
+    assert sorted(os.listdir(tmp_path / "out")) == ["hard_b32.npy", "soft8_b16.npy"]
+    for i, name in enumerate(("hard_b32", "soft8_b16")):
+        a = np.load(tmp_path / "out" / (name + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (d["config"]["parity"]["paths"][name + "[batch 0]"]["words"],)
+        w = a.astype(np.uint32)
+        assert np.array_equal(w.astype(np.float64), a)
+        assert int(np.bitwise_xor.reduce(w)) == int(d["checksums"][0][i], 16)
+
+
 @pytest.mark.gpu
 def test_bench_under_torchrun_one_rank():
     """`torch.distributed.run --nproc-per-node 1 bench.py --gpus 1`: the launcher's environment, RCCL group
     with device_id, barrier, max over ranks, checksum gather and the gather to rank 0 on cuda tensors."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", str(bench.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-           "--steps", "4", "--warmup", "1", "--warm-s", "0.05", "--no-cpu-baseline", "--no-llr", "--no-pcie",
+           "--steps", "4", "--warmup", "1", "--warm-s", "0.05", "--full", "--no-cpu-baseline", "--no-llr", "--no-pcie",
            "--no-channel", "--no-other"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]

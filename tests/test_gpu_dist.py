@@ -64,7 +64,7 @@ def test_batch_shard_rehearsal_equals_one_rank():
     run's, whose parity block checks batches 0 and 3 against the oracle, and the final gather reaches rank 0
     with every rank's words intact."""
     import bench
-    flags = ["--warmup", "1", "--warm-s", "0", "--no-cpu-baseline", "--no-llr", "--no-pcie", "--no-channel",
+    flags = ["--warmup", "1", "--warm-s", "0", "--full", "--no-cpu-baseline", "--no-llr", "--no-pcie", "--no-channel",
              "--no-other"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VD_BENCH_REHEARSE_SHARED_GPU"):
