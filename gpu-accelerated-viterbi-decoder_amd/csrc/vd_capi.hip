@@ -25,7 +25,9 @@
 #include "vd_pack.h"
 #include "vd_mt.h"
 #include "vd_mtjump.h"
-#include "vd_segplan.h"
+#include "vd_plan.h"
+
+using namespace vd;  // the option helpers and the plan (vd_plan.h)
 
 namespace {
 
@@ -45,169 +47,22 @@ int fail(int code, const std::string& msg)
                         std::string(#expr) + ": " + hipGetErrorString(e_));                  \
     } while (0)
 
-int ch_of(int o) { return o & 0xF; }
-int met_of(int o) { return (o >> 4) & 0xF; }
-int out_of(int o) { return (o >> 8) & 0xF; }
-int comp_of(int o) { return (o >> 12) & 0xF; }
-int bpp_of(int o) { return out_of(o) == 1 ? 16 : 32; }
-
-bool valid(int o)
-{
-    if (o & ~0xFFFF) return false;
-    int ch = ch_of(o), me = met_of(o), out = out_of(o), cm = comp_of(o);
-    if (ch > 4 || me > 2 || out > 1 || cm > 1) return false;
-    // OptionsValid (viterbi.h:22-41)
-    if (ch == 2 && me == 2) return false;
-    if (ch == 3 && me == 2) return false;
-    if (ch == 3 && me == 1) return false;
-    if (me == 2 && cm == 1) return false;
-    return true;
-}
-
-size_t input_size(int o, size_t n)
-{
-    switch (ch_of(o)) {
-    case 0: return (n + 7) / 8;
-    case 1: return (n + 1) / 2;
-    case 2: return n;
-    case 3: return n * 2;
-    case 4: return n * 4;
-    }
-    return 0;
-}
-size_t message_len(int o, size_t n)
-{
-    if (n / 2 < 64) return 0;  // the reference underflows here (size_t); rejected instead
-    size_t bpp = (size_t)bpp_of(o);
-    return (n / 2 - 64) / bpp * bpp;
-}
-// stages whose channel data lies in whole 32-bit words of the caller's buffer
-uint64_t avail_stages(int o, size_t n)
-{
-    size_t words = input_size(o, n) / 4;
-    uint64_t per = 0;
-    switch (ch_of(o)) {
-    case 0: per = words * 16; break;
-    case 1: per = words * 4; break;
-    case 2: per = words * 2; break;
-    case 3: per = words; break;
-    case 4: per = words / 2; break;
-    }
-    uint64_t half = n / 2;
-    return per < half ? per : half;
-}
-
 using launch_fn = void (*)(const void*, void*, vd::Geom, unsigned, hipStream_t);
 
-// workgroups of a launch without a segment table: one chunk per wave
-unsigned tg_grid(const vd::Geom& g)
-{
-    return (unsigned)(((uint64_t)g.nchunks * g.nbatch + vd::kWaves - 1) / vd::kWaves);
-}
-
-// one kernel per format (SOFT16 on int32 patterns, TgFmt::INT); CH >= kLlr: float channel values
-// quantised in the table build (fused SoftDecisionPacker)
-template <int CH, int CORE, int OB>
-void launch_t(const void* in, void* out, vd::Geom g, unsigned grid, hipStream_t s)
-{
-    hipLaunchKernelGGL((vd::vd_decode_tg<CH, CORE, OB>), dim3(grid), dim3(64 * vd::kWaves), 0, s, in, out, g);
-}
-
-template <int CH, int CORE>
-launch_fn pick_ob(int ob)
-{
-    return ob == 1 ? &launch_t<CH, CORE, 16> : &launch_t<CH, CORE, 32>;
-}
-
-// batched HARD / SOFT4 / FP32 launches: two chunks per wave in int16 halves (vd_kernel_pk.h)
-// (SPL: single-batch launches, one chunk per wave in both halves, vd_kernel_pk.h "split")
-template <int CH, int CORE, int OB, bool SPL>
-void launch_pk(const void* in, void* out, vd::Geom g, unsigned grid, hipStream_t s)
-{
-    hipLaunchKernelGGL((vd::vd_decode_pk<CH, CORE, OB, SPL>), dim3(grid), dim3(64 * vd::kWaves), 0, s, in, out, g);
-}
-template <int CH, int OB, bool SPL>
-launch_fn pick_pk_core(int me)
-{
-    return me == 0 ? &launch_pk<CH, 0, OB, SPL> : me == 1 ? &launch_pk<CH, 1, OB, SPL> : &launch_pk<CH, 2, OB, SPL>;
-}
-template <int CH, bool SPL>
-launch_fn pick_pk_ob(int o)
-{
-    return out_of(o) == 1 ? pick_pk_core<CH, 16, SPL>(met_of(o)) : pick_pk_core<CH, 32, SPL>(met_of(o));
-}
-template <bool SPL, int L>
-launch_fn pick_pk_ch(int o)
-{
-    switch (ch_of(o)) {
-    case 0: return pick_pk_ob<L + vd::HARD, SPL>(o);
-    case 1: return pick_pk_ob<L + vd::SOFT4, SPL>(o);
-    // (SOFT8 single batches: the split kernel is 9 % faster than vd_decode_tg's segment launch on codewords
-    // and, with the early-stop re-decodes, 18 % slower on noise-only input: DESIGN.md 4.3)
-    case 2:
-        return out_of(o) == 1 ? (met_of(o) == 0 ? &launch_pk<L + vd::SOFT8, 0, 16, SPL> : &launch_pk<L + vd::SOFT8, 1, 16, SPL>)
-                              : (met_of(o) == 0 ? &launch_pk<L + vd::SOFT8, 0, 32, SPL> : &launch_pk<L + vd::SOFT8, 1, 32, SPL>);
-    case 4: return pick_pk_ob<L + vd::FP32, SPL>(o);
+// one launcher per kernel; vd_plan.h's launcher<Launch>() makes the table of them
+struct Launch {
+    using fn = launch_fn;
+    template <int CH, int CORE, int OB>
+    static void tg(const void* in, void* out, vd::Geom g, unsigned grid, hipStream_t s)
+    {
+        hipLaunchKernelGGL((vd::vd_decode_tg<CH, CORE, OB>), dim3(grid), dim3(64 * vd::kWaves), 0, s, in, out, g);
     }
-    return nullptr;
-}
-template <bool SPL>
-launch_fn pick_pk(int o, bool llr)
-{
-    return llr ? pick_pk_ch<SPL, vd::kLlr>(o) : pick_pk_ch<SPL, 0>(o);
-}
-template <int L>
-launch_fn pick_ch(int o)
-{
-    const int ch = ch_of(o), me = met_of(o), ob = out_of(o);
-    switch (ch) {
-    case 0: return me == 0 ? pick_ob<L + 0, 0>(ob) : me == 1 ? pick_ob<L + 0, 1>(ob) : pick_ob<L + 0, 2>(ob);
-    case 1: return me == 0 ? pick_ob<L + 1, 0>(ob) : me == 1 ? pick_ob<L + 1, 1>(ob) : pick_ob<L + 1, 2>(ob);
-    case 2: return me == 0 ? pick_ob<L + 2, 0>(ob) : pick_ob<L + 2, 1>(ob);
-    case 3: return pick_ob<L + 3, 0>(ob);
-    case 4: return me == 0 ? pick_ob<L + 4, 0>(ob) : me == 1 ? pick_ob<L + 4, 1>(ob) : pick_ob<L + 4, 2>(ob);
+    template <int CH, int CORE, int OB, bool SPL>
+    static void pk(const void* in, void* out, vd::Geom g, unsigned grid, hipStream_t s)
+    {
+        hipLaunchKernelGGL((vd::vd_decode_pk<CH, CORE, OB, SPL>), dim3(grid), dim3(64 * vd::kWaves), 0, s, in, out, g);
     }
-    return nullptr;
-}
-launch_fn pick(int o, bool llr)
-{
-    return llr ? pick_ch<vd::kLlr>(o) : pick_ch<0>(o);
-}
-
-// CORE names the option's tie rule.  vd_decode_tg computes on the fp32 exact-integer tagged core (SOFT16:
-// int32 patterns); vd_decode_pk (HARD / SOFT4 / SOFT8 / FP32) on exact-integer tagged int16 halves, two
-// chunks per lane; none on fp16 arithmetic
-const char* kname(int o)
-{
-    static const char* names[5][3] = {
-        {"vd_decode_pk<HARD,B32> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<HARD,B32> (single batches with chunks under 64 words); M_B32 tie rule",
-         "vd_decode_pk<HARD,B16> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<HARD,B16> (single batches with chunks under 64 words); M_B16 tie rule",
-         "vd_decode_pk<HARD,F16> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<HARD,F16> (single batches with chunks under 64 words); M_FP16 tie rule"},
-        {"vd_decode_pk<SOFT4,B32> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<SOFT4,B32> (single batches with chunks under 64 words); M_B32 tie rule",
-         "vd_decode_pk<SOFT4,B16> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<SOFT4,B16> (single batches with chunks under 64 words); M_B16 tie rule",
-         "vd_decode_pk<SOFT4,F16> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<SOFT4,F16> (single batches with chunks under 64 words); M_FP16 tie rule"},
-        {"vd_decode_pk<SOFT8,B32> (int16 halves, 2-stage fields: batched, two chunks per lane; single batch, one "
-         "chunk cut in two) / vd_decode_tg<SOFT8,B32> (single batches with chunks under 64 words); M_B32 tie rule",
-         "vd_decode_pk<SOFT8,B16> (int16 halves, 2-stage fields: batched, two chunks per lane; single batch, one "
-         "chunk cut in two) / vd_decode_tg<SOFT8,B16> (single batches with chunks under 64 words); M_B16 tie rule",
-         "-"},
-        {"vd_decode_tg<SOFT16,B32> (int32 tagged patterns, M_B32 tie rule)", "-", "-"},
-        {"vd_decode_pk<FP32,B32> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<FP32,B32> (single batches with chunks under 64 words); M_B32 tie rule",
-         "vd_decode_pk<FP32,B16> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<FP32,B16> (single batches with chunks under 64 words); M_B16 tie rule",
-         "vd_decode_pk<FP32,F16> (int16 halves: batched, two chunks per lane; single batch, one chunk cut in two) / "
-         "vd_decode_tg<FP32,F16> (single batches with chunks under 64 words); M_FP16 tie rule"},
-    };
-    if (!valid(o)) return "-";
-    return names[ch_of(o)][met_of(o)];
-}
+};
 
 }  // namespace
 
@@ -240,30 +95,25 @@ struct vd_decoder {
     size_t cap2_in = 0, cap2_out = 0;
     hipStream_t s_in = nullptr, s_out = nullptr;
     DeviceState* ds = nullptr;  // the device's board / segment tables (looked up once, vd_create)
-    int split = 1;              // segment launches: 0 none (VD_NO_SPLIT=1), 1 pieces, 2 thirds, 3 sevenths (VD_SPLIT=...)
-    int pk = 1;                 // HARD/SOFT4/FP32 launches on vd_decode_pk (VD_NO_PK=1: on vd_decode_tg)
-    int pksplit = 1;            // their single-batch launches split on vd_decode_pk (VD_PK_SPLIT=0: tg segments)
-    int pktail = 1;             // ... with the tail chunks in 4-wave workgroups (VD_PK_TAIL=0: one chunk per wave)
+    Knobs knobs;                // VD_NO_SPLIT / VD_SPLIT / VD_NO_PK / VD_PK_SPLIT / VD_PK_TAIL as read at vd_create
     uint32_t* check = nullptr;  // LDS guard violation counter (vd_set_guard_check), null = off
 };
 
+// a device buffer of at least need bytes (contents not kept)
+static int grow(void*& p, size_t& cap, size_t need)
+{
+    if (need <= cap) return VD_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    VD_HIP(hipMalloc(&p, need));
+    cap = need;
+    return VD_OK;
+}
 static int ensure_capacity(vd_decoder* d, size_t inBytes, size_t outBytes)
 {
-    if (inBytes > d->cap_in) {
-        if (d->in_d) (void)hipFree(d->in_d);
-        d->in_d = nullptr;
-        d->cap_in = 0;
-        VD_HIP(hipMalloc(&d->in_d, inBytes));
-        d->cap_in = inBytes;
-    }
-    if (outBytes > d->cap_out) {
-        if (d->out_d) (void)hipFree(d->out_d);
-        d->out_d = nullptr;
-        d->cap_out = 0;
-        VD_HIP(hipMalloc(&d->out_d, outBytes));
-        d->cap_out = outBytes;
-    }
-    return VD_OK;
+    int rc = grow(d->in_d, d->cap_in, inBytes);
+    return rc != VD_OK ? rc : grow(d->out_d, d->cap_out, outBytes);
 }
 
 // Per-device state shared by every decoder and stream on a device, allocated once per device:
@@ -276,15 +126,12 @@ static int ensure_capacity(vd_decoder* d, size_t inBytes, size_t outBytes)
 //    differing; never expected, and vd_run / vd_run_stream fail when it is non-zero).
 // Segment launches keep their boundary vectors in LDS, so launches on any number of streams share no
 // scratch.  A decoder looks the state up once (vd_create), not per launch.
-struct SegTable {
-    uint32_t* d = nullptr;  // first chunk of each workgroup, then the chunk count
-    unsigned nwg = 0;
-};
 struct DeviceState {
     uint32_t* board = nullptr;
     int nsimd = 0;
     uint32_t* stats = nullptr;
-    SegTable pieces, thirds, sevenths;
+    uint32_t* seg[3] = {};  // by SegMode: first chunk of each workgroup, then the chunk count; null = no table
+    unsigned segWG[3] = {};  // ... and its workgroups
 };
 static DeviceState* device_state(int device)
 {
@@ -304,10 +151,9 @@ static DeviceState* device_state(int device)
         for (int th = 0; th < 3 && ok; th++) {
             const std::vector<uint32_t> t = vd::seg_table(x->nsimd, th);
             if (t.empty()) continue;
-            SegTable& T = th == vd::kSegSevenths ? x->sevenths : th == vd::kSegThirds ? x->thirds : x->pieces;
-            ok = hipMalloc(&T.d, t.size() * 4) == hipSuccess &&
-                 hipMemcpy(T.d, t.data(), t.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-            T.nwg = (unsigned)(t.size() - 1);
+            ok = hipMalloc(&x->seg[th], t.size() * 4) == hipSuccess &&
+                 hipMemcpy(x->seg[th], t.data(), t.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+            x->segWG[th] = (unsigned)(t.size() - 1);
         }
         if (!ok || hipDeviceSynchronize() != hipSuccess) {
             delete x;
@@ -317,51 +163,25 @@ static DeviceState* device_state(int device)
     }
     return st[device];
 }
-// Segment launch when the chunks are long enough and the device has a table; returns the grid
-static unsigned plan_split(vd::Geom& g, int options, const DeviceState* x, int mode)
+// Which kernel, launch form and grid a decode takes: vd_plan.h, for this decoder's knobs and device
+static LaunchPlan plan_of(const vd_decoder* d, size_t inputNum, uint32_t nbatch, bool llr)
 {
-    const uint64_t words32 = out_of(options) != 0 ? g.packNum / 2 : g.packNum;  // O_B16: 16-bit words
-    if (mode == 0 || g.nchunks != (uint32_t)vd::kChunks || words32 / g.nchunks < (uint64_t)vd::kSplitMinWords)
-        return tg_grid(g);
-    const SegTable& T = mode == 2 && x->thirds.d ? x->thirds : mode == 3 && x->sevenths.d ? x->sevenths : x->pieces;
-    if (!T.d) return tg_grid(g);
-    g.seg = T.d;
-    g.stats = x->stats;
-    return T.nwg;
-}
-
-// Which kernel and launch form a decode takes (launch_decode and vd_decoder_kernel_name share it):
-// batched launches of HARD/SOFT4/SOFT8/FP32 on vd_decode_pk (two chunks per wave); single batches of
-// HARD/SOFT4/SOFT8/FP32 with chunks of >= kSplitMinWords words on vd_decode_pk's split kernel; the rest on
-// vd_decode_tg (segment launch when plan_split finds a table, else one chunk per wave).
-enum class Form { PkBatched, PkSplit, Tg };
-static Form plan_form(const vd_decoder* d, uint64_t packNum, uint32_t nbatch, bool llr)
-{
-    const int options = d->options;
-    if (nbatch > 1 && d->pk && vd::kChunks % (2 * vd::kWaves) == 0 && pick_pk<false>(options, llr)) return Form::PkBatched;
-    const uint64_t w32 = out_of(options) != 0 ? packNum / 2 : packNum;
-    const bool splitok = nbatch == 1 && d->pk && d->pksplit && d->split && vd::kChunks % vd::kWaves == 0 &&
-                         w32 / vd::kChunks >= (uint64_t)vd::kSplitMinWords;
-    if (splitok && pick_pk<true>(options, llr)) return Form::PkSplit;
-    return Form::Tg;
+    return plan_launch(d->options, inputNum, nbatch, llr, d->knobs, d->ds->nsimd, d->ds->segWG);
 }
 
 // llr: in_d holds inputNum float channel values, quantised in the kernel (scale = packer scale).
 // nbatch > 1: batch b at in_d + b * inStride, out_d + b * outStride, all in one launch (never split).
+// *form: the launch form taken (the blocking entry points' split-cap check wants it)
 static int launch_decode(const vd_decoder* d, const void* in_d, void* out_d, size_t inputNum, hipStream_t s,
-                         bool llr = false, float scale = 1.0f, uint32_t nbatch = 1, uint64_t inStride = 0,
-                         uint64_t outStride = 0)
+                         Form* form = nullptr, bool llr = false, float scale = 1.0f, uint32_t nbatch = 1,
+                         uint64_t inStride = 0, uint64_t outStride = 0)
 {
     const int options = d->options;
-    launch_fn f = pick(options, llr);
+    const LaunchPlan p = plan_of(d, inputNum, nbatch, llr);
+    if (form) *form = p.form;
+    launch_fn f = launcher<Launch>(p.form, llr, ch_of(options), met_of(options), out_of(options) == 1);
     if (!f) return fail(VD_ERR_OPTIONS, "invalid options");
-    size_t msg = message_len(options, inputNum);
-    vd::Geom g;
-    g.packNum = msg / (size_t)bpp_of(options);
-    g.availStages = llr ? inputNum / 2 : avail_stages(options, inputNum);
-    g.nchunks = vd::kChunks;
-    g.scale = scale;
-    if (g.packNum == 0) return VD_OK;
+    if (!p.launches) return VD_OK;
     // the launch goes to the stream's device (the null stream: the current device); the board and the
     // guard counter belong to the decoder's device
     int sdev = -1;
@@ -370,33 +190,20 @@ static int launch_decode(const vd_decoder* d, const void* in_d, void* out_d, siz
     if (sdev != d->device)
         return fail(VD_ERR_ARG, "stream on device " + std::to_string(sdev) + ", decoder on device " +
                                     std::to_string(d->device));
+    vd::Geom g;
+    g.packNum = p.packNum;
+    g.availStages = llr ? inputNum / 2 : avail_stages(options, inputNum);
+    g.nchunks = vd::kChunks;
+    g.scale = scale;
     g.fair = d->ds->board;
     g.check = d->check;
     g.nbatch = nbatch;
     g.inStride = inStride;
     g.outStride = outStride;
-    const Form form = plan_form(d, g.packNum, nbatch, llr);
-    if (form == Form::PkBatched) {  // two chunks per wave: nchunks * nbatch / 8 workgroups
-        pick_pk<false>(options, llr)(in_d, out_d, g, (unsigned)((uint64_t)g.nchunks * nbatch / (2 * vd::kWaves)), s);
-        VD_HIP(hipGetLastError());
-        return VD_OK;
-    }
-    if (form == Form::PkSplit) {  // single batch: one chunk per wave, cut in two halves (nchunks / 4 workgroups)
-        g.stats = d->ds->stats;
-        // the last nchunks mod (SIMDs) chunks one per workgroup of 4 waves (8 parts each): with 6400 chunks
-        // on 1024 SIMDs every SIMD then runs 6 whole-chunk waves and one short one (vd_kernel_pk.h "split")
-        const uint32_t per = (uint32_t)d->ds->nsimd, tailc = per ? g.nchunks % per : 0u;
-        unsigned grid = g.nchunks / vd::kWaves;
-        if (d->pktail && tailc) {
-            g.tailWG = (g.nchunks - tailc) / vd::kWaves;
-            grid = g.tailWG + tailc;
-        }
-        pick_pk<true>(options, llr)(in_d, out_d, g, grid, s);
-        VD_HIP(hipGetLastError());
-        return VD_OK;
-    }
-    const unsigned grid = nbatch == 1 ? plan_split(g, options, d->ds, d->split) : tg_grid(g);
-    f(in_d, out_d, g, grid, s);
+    g.tailWG = p.tailWG;
+    if (p.seg != kSegNone) g.seg = d->ds->seg[p.seg];
+    if (p.stats) g.stats = d->ds->stats;
+    f(in_d, out_d, g, p.grid, s);
     VD_HIP(hipGetLastError());
     return VD_OK;
 }
@@ -430,31 +237,21 @@ int vd_split_cap_exits(int device, uint64_t* count)
     return VD_OK;
 }
 const char* vd_last_error(void) { return g_err.c_str(); }
-const char* vd_kernel_name(int options) { return kname(options); }
+const char* vd_kernel_name(int options)
+{
+    static const std::vector<std::string> names = [] {
+        std::vector<std::string> v;
+        for (int o = 0; o < 0x100; o++) v.push_back(option_kernels(o));
+        return v;
+    }();
+    return valid(options) ? names[options & 0xFF].c_str() : "-";
+}
 
 const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, int llr)
 {
     static thread_local std::string name;
     if (!d || nbatch < 1) return "-";
-    static const char* chs[5] = {"HARD", "SOFT4", "SOFT8", "SOFT16", "FP32"};
-    static const char* cores[3] = {"B32", "B16", "F16"};
-    const int o = d->options;
-    const uint64_t packNum = message_len(o, inputNum) / (size_t)bpp_of(o);
-    if (packNum == 0) return "-";  // launch_decode launches nothing
-    const std::string args = std::string(llr ? "LLR+" : "") + chs[ch_of(o)] + "," + cores[met_of(o)] + "," +
-                             (out_of(o) ? "O16" : "O32") + ">";
-    vd::Geom g;
-    g.packNum = packNum;
-    g.nchunks = vd::kChunks;
-    switch (plan_form(d, packNum, (uint32_t)nbatch, llr != 0)) {
-    case Form::PkBatched: name = "vd_decode_pk<" + args + " batched: two chunks per wave, int16 halves"; break;
-    case Form::PkSplit: name = "vd_decode_pk<" + args + " split: one chunk per wave cut in two, int16 halves"; break;
-    default:
-        if (nbatch == 1) (void)plan_split(g, o, d->ds, d->split);
-        name = "vd_decode_tg<" + args + (g.seg ? " segment launch: one chunk or piece per wave, fp32 tagged core"
-                                               : " one chunk per wave, fp32 tagged core");
-        if (ch_of(o) == 3) name.replace(name.find("fp32 tagged core"), 16, "int32 tagged patterns");
-    }
+    name = plan_name(plan_of(d, inputNum, (uint32_t)nbatch, llr != 0), d->options, llr != 0);
     return name.c_str();
 }
 
@@ -482,15 +279,7 @@ int vd_create(int options, size_t preallocInputNum, int device, vd_decoder** out
         delete d;
         return fail(VD_ERR_NOMEM, "per-device decode state allocation failed");
     }
-    const char* nosplit = std::getenv("VD_NO_SPLIT");
-    const char* smode = std::getenv("VD_SPLIT");
-    d->split = nosplit && nosplit[0] == '1' ? 0 : smode && !strcmp(smode, "thirds") ? 2 : smode && !strcmp(smode, "sevenths") ? 3 : 1;
-    const char* nopk = std::getenv("VD_NO_PK");
-    d->pk = nopk && nopk[0] == '1' ? 0 : 1;
-    const char* pks = std::getenv("VD_PK_SPLIT");
-    d->pksplit = pks && pks[0] == '0' ? 0 : 1;
-    const char* pkt = std::getenv("VD_PK_TAIL");
-    d->pktail = pkt && pkt[0] == '0' ? 0 : 1;
+    d->knobs = knobs_from_env();
     const char* chk = std::getenv("VD_CHECK");
     if (chk && chk[0] == '1') {
         int rc = vd_set_guard_check(d, 1);
@@ -531,16 +320,32 @@ int vd_destroy(vd_decoder* d)
 
 // vd_run / vd_run_stream (blocking): a single-batch split launch whose re-decode passes hit their cap with a part
 // still differing (vd_kernel_pk.h "Split"; never expected) fails the call instead of returning wrong words
-static int check_split_cap(const vd_decoder* d, size_t inputNum, bool llr = false)
+static int check_split_cap(const vd_decoder* d, Form form)
 {
-    const uint64_t packNum = message_len(d->options, inputNum) / (size_t)bpp_of(d->options);
-    if (packNum == 0 || plan_form(d, packNum, 1, llr) != Form::PkSplit) return VD_OK;
+    if (form != Form::PkSplit) return VD_OK;
     uint32_t v = 0;
     VD_HIP(hipMemcpy(&v, d->ds->stats + 1, 4, hipMemcpyDeviceToHost));
     if (v)
         return fail(VD_ERR_DEVICE, "split launch reached its re-decode pass cap with a part still differing (" +
                                        std::to_string(v) + " waves on this device so far): decoded words may be wrong");
     return VD_OK;
+}
+
+// the blocking decode through the decoder's device buffers: in_h to in_d, the launch between the timing
+// events, out_d to out_h, kernel-only time
+static int run_staged(vd_decoder* d, void* in_d, const void* in_h, size_t inB, void* out_h, size_t outB, size_t inputNum,
+                      bool llr, float scale, float* kernel_ms)
+{
+    Form form = Form::Tg;
+    VD_HIP(hipMemcpyAsync(in_d, in_h, inB, hipMemcpyHostToDevice, d->stream));
+    VD_HIP(hipEventRecord(d->ev0, d->stream));
+    int rc = launch_decode(d, in_d, d->out_d, inputNum, d->stream, &form, llr, scale);
+    if (rc != VD_OK) return rc;
+    VD_HIP(hipEventRecord(d->ev1, d->stream));
+    VD_HIP(hipMemcpyAsync(out_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
+    VD_HIP(hipStreamSynchronize(d->stream));
+    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    return check_split_cap(d, form);
 }
 
 int vd_run(vd_decoder* d, const void* input_h, void* output_h, size_t inputNum, float* kernel_ms)
@@ -552,25 +357,18 @@ int vd_run(vd_decoder* d, const void* input_h, void* output_h, size_t inputNum, 
     void* zin = mapped_host(input_h);
     void* zout = zin ? mapped_host(output_h) : nullptr;
     if (zin && zout) {  // pinned host buffers: zero-copy decode (kernel_ms then includes the PCIe traffic)
+        Form form = Form::Tg;
         VD_HIP(hipEventRecord(d->ev0, d->stream));
-        int rc = launch_decode(d, zin, zout, inputNum, d->stream);
+        int rc = launch_decode(d, zin, zout, inputNum, d->stream, &form);
         if (rc != VD_OK) return rc;
         VD_HIP(hipEventRecord(d->ev1, d->stream));
         VD_HIP(hipStreamSynchronize(d->stream));
         if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-        return check_split_cap(d, inputNum);
+        return check_split_cap(d, form);
     }
     int rc = ensure_capacity(d, inB, outB + 16);
     if (rc != VD_OK) return rc;
-    VD_HIP(hipMemcpyAsync(d->in_d, input_h, inB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    rc = launch_decode(d, d->in_d, d->out_d, inputNum, d->stream);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return check_split_cap(d, inputNum);
+    return run_staged(d, d->in_d, input_h, inB, output_h, outB, inputNum, false, 1.0f, kernel_ms);
 }
 
 int vd_set_guard_check(vd_decoder* d, int enable)
@@ -604,28 +402,33 @@ int vd_guard_violations(vd_decoder* d, uint64_t* count)
     return VD_OK;
 }
 
+// vd_run_device*: the argument checks, then one launch (the single-batch entry points: nbatch 1, strides 0).
+// in_stride: any multiple of its alignment (0 = every batch decodes the same input); inputs are only read,
+// so overlapping windows (e.g. sliding) are valid
+static int run_device(vd_decoder* d, const void* in_d, void* out_d, size_t inputNum, void* stream, bool llr, float scale,
+                      int nbatch, size_t in_stride, size_t output_stride)
+{
+    if (!d || !in_d || !out_d) return fail(VD_ERR_ARG, "null argument");
+    if (nbatch < 1) return fail(VD_ERR_ARG, "nbatch must be >= 1");
+    if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
+    if (nbatch > 1 && output_stride < message_len(d->options, inputNum) / 8)
+        return fail(VD_ERR_ARG, "output_stride smaller than the output size: batches would overlap");
+    if ((uint64_t)vd::kChunks * (uint64_t)nbatch > 0xFFFFFFFFull) return fail(VD_ERR_ARG, "nbatch too large");
+    if (llr && ((in_stride & 15) || (output_stride & 3))) return fail(VD_ERR_ARG, "llr_stride % 16 or output_stride % 4 != 0");
+    if (!llr && ((in_stride | output_stride) & 3)) return fail(VD_ERR_ARG, "strides must be multiples of 4 bytes");
+    return launch_decode(d, in_d, out_d, inputNum, (hipStream_t)stream, nullptr, llr, scale, (uint32_t)nbatch, in_stride,
+                         output_stride);
+}
+
 int vd_run_device(vd_decoder* d, const void* input_d, void* output_d, size_t inputNum, void* stream)
 {
-    if (!d || !input_d || !output_d) return fail(VD_ERR_ARG, "null argument");
-    if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
-    return launch_decode(d, input_d, output_d, inputNum, (hipStream_t)stream);
+    return run_device(d, input_d, output_d, inputNum, stream, false, 1.0f, 1, 0, 0);
 }
 
 int vd_run_device_batch(vd_decoder* d, const void* input_d, size_t input_stride, void* output_d, size_t output_stride,
                         size_t inputNum, int nbatch, void* stream)
 {
-    if (!d || !input_d || !output_d) return fail(VD_ERR_ARG, "null argument");
-    if (nbatch < 1) return fail(VD_ERR_ARG, "nbatch must be >= 1");
-    if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
-    if (nbatch > 1 && output_stride < message_len(d->options, inputNum) / 8)
-        return fail(VD_ERR_ARG, "output_stride smaller than the output size: batches would overlap");
-    // input_stride: any (0 = every batch decodes the same input); inputs are only read, so overlapping
-    // windows (e.g. sliding) are valid
-    if ((uint64_t)vd::kChunks * (uint64_t)nbatch > 0xFFFFFFFFull) return fail(VD_ERR_ARG, "nbatch too large");
-    if ((input_stride | output_stride) & 3) return fail(VD_ERR_ARG, "strides must be multiples of 4 bytes");
-    if (nbatch == 1) return launch_decode(d, input_d, output_d, inputNum, (hipStream_t)stream);
-    return launch_decode(d, input_d, output_d, inputNum, (hipStream_t)stream, false, 1.0f, (uint32_t)nbatch, input_stride,
-                         output_stride);
+    return run_device(d, input_d, output_d, inputNum, stream, false, 1.0f, nbatch, input_stride, output_stride);
 }
 
 static int launch_pack(int options, const float* llr_d, size_t inputNum, float scale, void* packed_d, hipStream_t s)
@@ -635,14 +438,11 @@ static int launch_pack(int options, const float* llr_d, size_t inputNum, float s
     const int per = ch == 0 ? 32 : ch == 1 ? 8 : ch == 2 ? 4 : ch == 3 ? 2 : 1;
     const uint64_t nw = (inputNum + per - 1) / per;
     if (nw == 0) return VD_OK;
-    const dim3 blk(256), grd((unsigned)((nw + 255) / 256));
-    switch (ch) {
-    case 0: hipLaunchKernelGGL(vd::pack_llr<0>, grd, blk, 0, s, llr_d, (uint64_t)inputNum, scale, packed_d); break;
-    case 1: hipLaunchKernelGGL(vd::pack_llr<1>, grd, blk, 0, s, llr_d, (uint64_t)inputNum, scale, packed_d); break;
-    case 2: hipLaunchKernelGGL(vd::pack_llr<2>, grd, blk, 0, s, llr_d, (uint64_t)inputNum, scale, packed_d); break;
-    case 3: hipLaunchKernelGGL(vd::pack_llr<3>, grd, blk, 0, s, llr_d, (uint64_t)inputNum, scale, packed_d); break;
-    case 4: hipLaunchKernelGGL(vd::pack_llr<4>, grd, blk, 0, s, llr_d, (uint64_t)inputNum, scale, packed_d); break;
-    }
+    static void (*const kernels[5])(const float*, uint64_t, float, void*) = {
+        vd::pack_llr<0>, vd::pack_llr<1>, vd::pack_llr<2>, vd::pack_llr<3>, vd::pack_llr<4>};
+    if (ch < 5)
+        hipLaunchKernelGGL(kernels[ch], dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, llr_d, (uint64_t)inputNum, scale,
+                           packed_d);
     VD_HIP(hipGetLastError());
     return VD_OK;
 }
@@ -656,24 +456,13 @@ int vd_pack_device(int options, const float* llr_d, size_t inputNum, float scale
 
 int vd_run_device_llr(vd_decoder* d, const float* llr_d, void* output_d, size_t inputNum, float scale, void* stream)
 {
-    if (!d || !llr_d || !output_d) return fail(VD_ERR_ARG, "null argument");
-    if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
-    return launch_decode(d, llr_d, output_d, inputNum, (hipStream_t)stream, true, scale);
+    return run_device(d, llr_d, output_d, inputNum, stream, true, scale, 1, 0, 0);
 }
 
 int vd_run_device_llr_batch(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
                             size_t inputNum, float scale, int nbatch, void* stream)
 {
-    if (!d || !llr_d || !output_d) return fail(VD_ERR_ARG, "null argument");
-    if (nbatch < 1) return fail(VD_ERR_ARG, "nbatch must be >= 1");
-    if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
-    if (nbatch > 1 && output_stride < message_len(d->options, inputNum) / 8)
-        return fail(VD_ERR_ARG, "output_stride smaller than the output size: batches would overlap");
-    if ((uint64_t)vd::kChunks * (uint64_t)nbatch > 0xFFFFFFFFull) return fail(VD_ERR_ARG, "nbatch too large");
-    if ((llr_stride & 15) || (output_stride & 3)) return fail(VD_ERR_ARG, "llr_stride % 16 or output_stride % 4 != 0");
-    if (nbatch == 1) return launch_decode(d, llr_d, output_d, inputNum, (hipStream_t)stream, true, scale);
-    return launch_decode(d, llr_d, output_d, inputNum, (hipStream_t)stream, true, scale, (uint32_t)nbatch, llr_stride,
-                         output_stride);
+    return run_device(d, llr_d, output_d, inputNum, stream, true, scale, nbatch, llr_stride, output_stride);
 }
 
 int vd_run_llr(vd_decoder* d, const float* llr_h, void* output_h, size_t inputNum, float scale, float* kernel_ms)
@@ -682,24 +471,10 @@ int vd_run_llr(vd_decoder* d, const float* llr_h, void* output_h, size_t inputNu
     if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
     const size_t inB = inputNum * sizeof(float), outB = message_len(d->options, inputNum) / 8;
     VD_HIP(hipSetDevice(d->device));
-    if (inB > d->cap_llr) {
-        if (d->llr_d) (void)hipFree(d->llr_d);
-        d->llr_d = nullptr;
-        d->cap_llr = 0;
-        VD_HIP(hipMalloc(&d->llr_d, inB));
-        d->cap_llr = inB;
-    }
-    int rc = ensure_capacity(d, 0, outB + 16);
+    int rc = grow(d->llr_d, d->cap_llr, inB);
+    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
     if (rc != VD_OK) return rc;
-    VD_HIP(hipMemcpyAsync(d->llr_d, llr_h, inB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    rc = vd_run_device_llr(d, (const float*)d->llr_d, d->out_d, inputNum, scale, d->stream);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return check_split_cap(d, inputNum, true);
+    return run_staged(d, d->llr_d, llr_h, inB, output_h, outB, inputNum, true, scale, kernel_ms);
 }
 
 void* vd_host_alloc(size_t bytes)
@@ -728,36 +503,25 @@ int vd_run_stream(vd_decoder* d, const void* const* input_h, void* const* output
     if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
     const size_t inB = input_size(d->options, inputNum), outB = message_len(d->options, inputNum) / 8;
     VD_HIP(hipSetDevice(d->device));
+    Form form = Form::Tg;  // of the launches (all alike); no launch, no split-cap check
     // all buffers pinned: the kernels stream them over PCIe themselves, back to back on one stream
     bool zc = true;
     for (int b = 0; b < nbatches && zc; b++) zc = mapped_host(input_h[b]) && mapped_host(output_h[b]);
     if (zc) {
         auto t0 = std::chrono::steady_clock::now();
         for (int b = 0; b < nbatches; b++) {
-            int rc = launch_decode(d, mapped_host(input_h[b]), mapped_host(output_h[b]), inputNum, d->stream);
+            int rc = launch_decode(d, mapped_host(input_h[b]), mapped_host(output_h[b]), inputNum, d->stream, &form);
             if (rc != VD_OK) return rc;
         }
         VD_HIP(hipStreamSynchronize(d->stream));
         if (wall_ms)
             *wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return nbatches > 0 ? check_split_cap(d, inputNum) : VD_OK;
+        return check_split_cap(d, form);
     }
     int rc = ensure_capacity(d, inB, outB + 16);
+    if (rc == VD_OK) rc = grow(d->in2_d, d->cap2_in, inB);
+    if (rc == VD_OK) rc = grow(d->out2_d, d->cap2_out, outB + 16);
     if (rc != VD_OK) return rc;
-    if (inB > d->cap2_in) {
-        if (d->in2_d) (void)hipFree(d->in2_d);
-        d->in2_d = nullptr;
-        d->cap2_in = 0;
-        VD_HIP(hipMalloc(&d->in2_d, inB));
-        d->cap2_in = inB;
-    }
-    if (outB + 16 > d->cap2_out) {
-        if (d->out2_d) (void)hipFree(d->out2_d);
-        d->out2_d = nullptr;
-        d->cap2_out = 0;
-        VD_HIP(hipMalloc(&d->out2_d, outB + 16));
-        d->cap2_out = outB + 16;
-    }
     if (!d->s_in) VD_HIP(hipStreamCreateWithFlags(&d->s_in, hipStreamNonBlocking));
     if (!d->s_out) VD_HIP(hipStreamCreateWithFlags(&d->s_out, hipStreamNonBlocking));
     void* ins[2] = {d->in_d, d->in2_d};
@@ -788,7 +552,7 @@ int vd_run_stream(vd_decoder* d, const void* const* input_h, void* const* output
             rc = fail(VD_ERR_DEVICE, "pipeline enqueue failed");
             break;
         }
-        rc = launch_decode(d, ins[k], outs[k], inputNum, d->stream);
+        rc = launch_decode(d, ins[k], outs[k], inputNum, d->stream, &form);
         if (rc != VD_OK) break;
         if (hipEventRecord(decoded[k], d->stream) != hipSuccess) { rc = fail(VD_ERR_DEVICE, "record"); break; }
         if (b + 1 < nbatches && (rc = h2d(b + 1)) != VD_OK) break;
@@ -810,7 +574,7 @@ int vd_run_stream(vd_decoder* d, const void* const* input_h, void* const* output
     if (rc != VD_OK) return rc;
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(VD_ERR_DEVICE, "pipeline failed");
     if (wall_ms) *wall_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    return nbatches > 0 ? check_split_cap(d, inputNum) : VD_OK;
+    return check_split_cap(d, form);
 }
 
 int vd_run_batches(int options, const void* const* input_h, void* const* output_h, size_t inputNum,

@@ -613,7 +613,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tg_rsrc(const void* in, uint64
 // barriers, so the last (verified) decode of every word is the one that stays.  Block boundaries inside
 // a chunk are multiples of 3 (the group length, 96 stages = 16 trellis periods) so every run uses the
 // same position <-> state map there.  The vectors never leave the workgroup's LDS, so concurrent launches
-// share no storage.  The host's tables (vd_capi.hip plan_split): 256 workgroups of one chunk in 4 pieces
+// share no storage.  The host's tables (vd_plan.h plan_launch): 256 workgroups of one chunk in 4 pieces
 // after 1536 of 4 whole chunks (7 waves per SIMD, round 2's split), or 1792 workgroups of 3 chunks and
 // 256 of 4 (8 waves of 3/4 chunk or 1 chunk per SIMD, their progress kept even by the fairness controller
 // in fractions of their work).

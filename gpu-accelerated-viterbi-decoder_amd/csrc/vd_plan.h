@@ -1,0 +1,224 @@
+// vd_plan.h -- which kernel, launch form and grid a decode takes, as a pure host-side function of the option,
+// the sizes, the knobs read at vd_create and the device's SIMD and segment-table counts (no HIP runtime calls,
+// no decoder: tests/cxx/plan_check.cpp checks it on the CPU), with the option helpers, the list of kernels
+// and the kernel names.  Shared by the C-ABI (vd_capi.hip) and the timing tools.
+// Include after vd_kernel_tg.h (kSplitMinWords, kLlr; the tools include their ablation copy of it).
+#pragma once
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include "vd_segplan.h"
+
+namespace vd {
+
+// ---------------------------------------------------------------- options (include/viterbi.h bit fields)
+inline int ch_of(int o) { return o & 0xF; }
+inline int met_of(int o) { return (o >> 4) & 0xF; }
+inline int out_of(int o) { return (o >> 8) & 0xF; }
+inline int comp_of(int o) { return (o >> 12) & 0xF; }
+inline int bpp_of(int o) { return out_of(o) == 1 ? 16 : 32; }
+
+inline bool valid(int o)
+{
+    if (o & ~0xFFFF) return false;
+    int ch = ch_of(o), me = met_of(o), out = out_of(o), cm = comp_of(o);
+    if (ch > 4 || me > 2 || out > 1 || cm > 1) return false;
+    // OptionsValid (viterbi.h:22-41)
+    if (ch == 2 && me == 2) return false;
+    if (ch == 3 && me == 2) return false;
+    if (ch == 3 && me == 1) return false;
+    if (me == 2 && cm == 1) return false;
+    return true;
+}
+
+inline size_t input_size(int o, size_t n)
+{
+    switch (ch_of(o)) {
+    case 0: return (n + 7) / 8;
+    case 1: return (n + 1) / 2;
+    case 2: return n;
+    case 3: return n * 2;
+    case 4: return n * 4;
+    }
+    return 0;
+}
+inline size_t message_len(int o, size_t n)
+{
+    if (n / 2 < 64) return 0;  // the reference underflows here (size_t); rejected instead
+    size_t bpp = (size_t)bpp_of(o);
+    return (n / 2 - 64) / bpp * bpp;
+}
+// stages whose channel data lies in whole 32-bit words of the caller's buffer
+inline uint64_t avail_stages(int o, size_t n)
+{
+    size_t words = input_size(o, n) / 4;
+    uint64_t per = 0;
+    switch (ch_of(o)) {
+    case 0: per = words * 16; break;
+    case 1: per = words * 4; break;
+    case 2: per = words * 2; break;
+    case 3: per = words; break;
+    case 4: per = words / 2; break;
+    }
+    uint64_t half = n / 2;
+    return per < half ? per : half;
+}
+
+// ---------------------------------------------------------------- the kernels
+// The valid (format, metric) pairs, written once.  vd_decode_tg has a kernel for each (SOFT16 on int32
+// patterns, TgFmt::INT); vd_decode_pk (two chunks per wave in int16 halves, vd_kernel_pk.h) for all but SOFT16.
+#define VD_PK_PAIRS(X) \
+    X(HARD, B32) X(HARD, B16) X(HARD, F16) X(SOFT4, B32) X(SOFT4, B16) X(SOFT4, F16) X(SOFT8, B32) X(SOFT8, B16) \
+    X(FP32, B32) X(FP32, B16) X(FP32, F16)
+#define VD_TG_PAIRS(X) VD_PK_PAIRS(X) X(SOFT16, B32)
+
+// launch form, and with it the kernel family: vd_decode_tg, vd_decode_pk<.., false>, vd_decode_pk<.., true>
+enum class Form : int { Tg = 0, PkBatched = 1, PkSplit = 2 };
+
+inline bool has_kernel(Form f, int ch, int me)
+{
+#define VD_X(C, M) if (ch == C && me == M) return true;
+    if (f == Form::Tg) { VD_TG_PAIRS(VD_X) } else { VD_PK_PAIRS(VD_X) }
+#undef VD_X
+    return false;
+}
+
+// The launcher of the kernel for (form, llr, format, metric, output width), null where none exists.  L gives
+// the pointer type L::fn and the launchers L::tg<CH, CORE, OB> and L::pk<CH, CORE, OB, SPL>, one kernel each
+// (vd_capi.hip; plan_check.cpp passes stubs): 12 pairs x {O32, O16} x {packed, LLR} of vd_decode_tg, 11 pairs
+// x {O32, O16} x {batched, SPL} x {packed, LLR} of vd_decode_pk.  llr: float channel values, quantised in
+// the table build (fused SoftDecisionPacker): channel ids kLlr + format.
+template <class L>
+typename L::fn launcher(Form f, bool llr, int ch, int me, bool o16)
+{
+    struct Table {
+        typename L::fn at[3][2][5][3][2] = {};
+        Table()
+        {
+            constexpr int T = (int)Form::Tg, B = (int)Form::PkBatched, S = (int)Form::PkSplit;
+#define VD_ROW(F, C, M, K, ...)                                   \
+    at[F][0][C][M][0] = &L::template K<C, M, 32 __VA_ARGS__>;        \
+    at[F][0][C][M][1] = &L::template K<C, M, 16 __VA_ARGS__>;        \
+    at[F][1][C][M][0] = &L::template K<kLlr + C, M, 32 __VA_ARGS__>; \
+    at[F][1][C][M][1] = &L::template K<kLlr + C, M, 16 __VA_ARGS__>;
+#define VD_X(C, M) VD_ROW(T, C, M, tg, )
+            VD_TG_PAIRS(VD_X)
+#undef VD_X
+#define VD_X(C, M) VD_ROW(B, C, M, pk, , false) VD_ROW(S, C, M, pk, , true)
+            VD_PK_PAIRS(VD_X)
+#undef VD_X
+#undef VD_ROW
+        }
+    };
+    static const Table t;
+    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[(int)f][llr][ch][me][o16] : nullptr;
+}
+
+// ---------------------------------------------------------------- the knobs (read once, at vd_create)
+struct Knobs {
+    int split = 1;    // segment launches: 0 none (VD_NO_SPLIT=1), 1 pieces, 2 thirds, 3 sevenths (VD_SPLIT=...)
+    int pk = 1;       // HARD/SOFT4/SOFT8/FP32 launches on vd_decode_pk (VD_NO_PK=1: on vd_decode_tg)
+    int pksplit = 1;  // their single-batch launches split on vd_decode_pk (VD_PK_SPLIT=0: tg segments)
+    int pktail = 1;   // ... with the tail chunks in 4-wave workgroups (VD_PK_TAIL=0: one chunk per wave)
+};
+inline Knobs knobs_from_env()
+{
+    auto is = [](const char* name, char c) { const char* v = std::getenv(name); return v && v[0] == c; };
+    const char* smode = std::getenv("VD_SPLIT");
+    Knobs k;
+    k.split = is("VD_NO_SPLIT", '1') ? 0 : smode && !strcmp(smode, "thirds") ? 2 : smode && !strcmp(smode, "sevenths") ? 3 : 1;
+    k.pk = is("VD_NO_PK", '1') ? 0 : 1;
+    k.pksplit = is("VD_PK_SPLIT", '0') ? 0 : 1;
+    k.pktail = is("VD_PK_TAIL", '0') ? 0 : 1;
+    return k;
+}
+
+// ---------------------------------------------------------------- the plan
+constexpr int kSegNone = -1;
+struct LaunchPlan {
+    bool launches = false;  // false: packNum == 0, nothing to decode (the other fields then mean nothing)
+    Form form = Form::Tg;
+    unsigned grid = 0;      // workgroups of kWaves waves
+    uint32_t tailWG = ~0u;  // Geom::tailWG (split launches with tail workgroups)
+    int seg = kSegNone;     // the SegMode of a segment launch's table (Geom::seg)
+    bool stats = false;     // Geom::stats set: segment and split launches count their re-decodes
+    uint64_t packNum = 0;   // Geom::packNum
+};
+
+// nbatch batches of inputNum encoded values on a device of nsimd SIMDs whose segment tables (vd_segplan.h,
+// indexed by SegMode) have segWG[] workgroups, 0 for an absent table:
+//  * batched launches of HARD/SOFT4/SOFT8/FP32 on vd_decode_pk, two chunks per wave: nchunks nbatch / 8 workgroups;
+//  * their single batches with chunks of >= kSplitMinWords 32-bit words on vd_decode_pk's split kernel, one
+//    chunk per wave cut in two halves (nchunks / 4 workgroups), the last nchunks mod nsimd chunks one per
+//    workgroup of 4 waves (8 parts each): with 6400 chunks on 1024 SIMDs every SIMD then runs 6 whole-chunk
+//    waves and one short one (vd_kernel_pk.h "split");
+//    (SOFT8: the split kernel is 9 % faster than vd_decode_tg's segment launch on codewords and, with the
+//    early-stop re-decodes, 18 % slower on noise-only input: DESIGN.md 4.3)
+//  * the rest on vd_decode_tg: a segment launch for single batches when the chunks are long enough and the
+//    device has a table (thirds and sevenths fall back to pieces), else one chunk per wave.
+// llr (float channel values) changes the kernel, never the plan: every kernel has its LLR twin.
+inline LaunchPlan plan_launch(int o, size_t inputNum, uint32_t nbatch, bool llr, const Knobs& k, int nsimd,
+                              const unsigned segWG[3])
+{
+    (void)llr;
+    LaunchPlan p;
+    p.packNum = message_len(o, inputNum) / (size_t)bpp_of(o);
+    p.launches = p.packNum != 0;
+    if (!p.launches) return p;
+    const uint32_t nch = kChunks;
+    const uint64_t words32 = out_of(o) != 0 ? p.packNum / 2 : p.packNum;  // O_B16: 16-bit words
+    const bool longChunks = nbatch == 1 && k.split && words32 / nch >= (uint64_t)kSplitMinWords;
+    if (nbatch > 1 && k.pk && nch % (2 * kWaves) == 0 && has_kernel(Form::PkBatched, ch_of(o), met_of(o))) {
+        p.form = Form::PkBatched;
+        p.grid = (unsigned)((uint64_t)nch * nbatch / (2 * kWaves));
+    } else if (longChunks && k.pk && k.pksplit && nch % kWaves == 0 && has_kernel(Form::PkSplit, ch_of(o), met_of(o))) {
+        p.form = Form::PkSplit;
+        p.stats = true;
+        const uint32_t tailc = nsimd > 0 ? nch % (uint32_t)nsimd : 0u;
+        p.grid = nch / kWaves;
+        if (k.pktail && tailc) {
+            p.tailWG = (nch - tailc) / kWaves;
+            p.grid = p.tailWG + tailc;
+        }
+    } else {
+        const int want = k.split - 1;  // the knob's SegMode
+        if (longChunks) p.seg = want > kSegPieces && segWG[want] ? want : segWG[kSegPieces] ? (int)kSegPieces : kSegNone;
+        p.stats = p.seg != kSegNone;
+        p.grid = p.stats ? segWG[p.seg] : (unsigned)(((uint64_t)nch * nbatch + kWaves - 1) / kWaves);
+    }
+    return p;
+}
+
+// ---------------------------------------------------------------- names
+inline constexpr const char* kChNames[5] = {"HARD", "SOFT4", "SOFT8", "SOFT16", "FP32"};
+inline constexpr const char* kCoreNames[3] = {"B32", "B16", "F16"};
+
+// vd_decoder_kernel_name: the kernel and launch form of one planned launch
+inline std::string plan_name(const LaunchPlan& p, int o, bool llr)
+{
+    if (!p.launches) return "-";
+    const std::string args = std::string(llr ? "LLR+" : "") + kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," +
+                             (out_of(o) ? "O16" : "O32") + ">";
+    if (p.form == Form::PkBatched) return "vd_decode_pk<" + args + " batched: two chunks per wave, int16 halves";
+    if (p.form == Form::PkSplit) return "vd_decode_pk<" + args + " split: one chunk per wave cut in two, int16 halves";
+    return "vd_decode_tg<" + args + (p.seg != kSegNone ? " segment launch: one chunk or piece per wave, " : " one chunk per wave, ") +
+           (ch_of(o) == SOFT16 ? "int32 tagged patterns" : "fp32 tagged core");
+}
+
+// vd_kernel_name: the kernels of an option.  The metric names the option's tie rule.  vd_decode_tg computes on
+// the fp32 exact-integer tagged core (SOFT16: int32 patterns); vd_decode_pk (HARD / SOFT4 / SOFT8 / FP32) on
+// exact-integer tagged int16 halves, two chunks per lane; none on fp16 arithmetic
+inline std::string option_kernels(int o)
+{
+    static const char* ties[3] = {"M_B32", "M_B16", "M_FP16"};
+    if (!valid(o)) return "-";
+    const std::string fm = std::string("<") + kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + ">";
+    if (!has_kernel(Form::PkBatched, ch_of(o), met_of(o)))
+        return "vd_decode_tg" + fm + " (int32 tagged patterns, " + ties[met_of(o)] + " tie rule)";
+    return "vd_decode_pk" + fm + " (int16 halves" + (ch_of(o) == SOFT8 ? ", 2-stage fields" : "") +
+           ": batched, two chunks per lane; single batch, one chunk cut in two) / vd_decode_tg" + fm +
+           " (single batches with chunks under " + std::to_string(kSplitMinWords) + " words); " + ties[met_of(o)] + " tie rule";
+}
+
+}  // namespace vd

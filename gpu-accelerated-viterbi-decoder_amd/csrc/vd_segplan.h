@@ -1,6 +1,6 @@
 // vd_segplan.h -- host-side segment tables of segment launches (vd_kernel_tg.h "segment launches"):
-// the first chunk of every workgroup, then the chunk count.  Shared by the C-ABI (vd_capi.hip) and the
-// timing tools.
+// the first chunk of every workgroup, then the chunk count.  Shared by the C-ABI (vd_capi.hip; vd_plan.h
+// plan_launch decides which launch uses which table) and the timing tools.
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -2,6 +2,7 @@
 declares, and its host-side logic (option filter, size helpers, reference harness, BER count)
 agrees with the oracle.  No decode is run here (no GPU in this container)."""
 import ctypes
+import json
 import os
 import re
 
@@ -74,6 +75,16 @@ def test_count_errors_matches_oracle(vd, vo):
     opt16 = opt | vo.O_B16
     dec16, _ = vo.decode(opt16, packed)
     assert vd.count_errors(opt16, bits, dec16) == vo.ben(opt16, bits, dec16)
+
+
+def test_kernel_names_match_recorded(vd):
+    """vd_kernel_name for every option value, valid or not, character for character as recorded from the library
+    before the names were built from parts (tests/golden/kernel_names.json; bench and profiler records quote them)."""
+    with open(os.path.join(ROOT, "tests", "golden", "kernel_names.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(f"0x{o:x}" for o in ALL_OPTIONS + [0x10000])
+    for o in ALL_OPTIONS + [0x10000]:
+        assert vd.kernel_name(o) == want[f"0x{o:x}"], hex(o)
 
 
 def test_invalid_options_raise(vd):

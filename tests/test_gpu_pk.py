@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from vitdec import FP32, HARD, M_B16, M_B32, M_FP16, O_B16, SOFT4, SOFT8
+from vitdec import FP32, HARD, M_B16, M_B32, M_FP16, O_B16, SOFT4, SOFT8, SOFT16
 from test_gpu_parity import name
 
 
@@ -214,3 +214,36 @@ def test_packed_soft8_extreme_inputs(gpu, vo, opt, kind):
             got1 = single.cpu().numpy().view(ref.dtype)
             bad = np.flatnonzero(got1 != ref)
             assert bad.size == 0, f"single launch: {bad.size} of {ref.size} words differ, first {bad[:5]}"
+
+
+@pytest.mark.gpu
+def test_decoder_kernel_names_follow_the_knobs(gpu):
+    """vd_decoder_kernel_name (the launch plan of vd_plan.h with this device's SIMD count and segment tables, which
+    tests/test_plan.py checks on the CPU for 1024 SIMDs) for the bench size, single and 20 batches, under
+    the knobs a decoder reads at creation.  Nothing is decoded."""
+    n = 64_000_000
+
+    def names(opt, env):
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            with gpu.ViterbiCUDA(opt) as dec:
+                return dec.kernel_for(n, 1), dec.kernel_for(n, 20)
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+
+    one, many = names(HARD | M_B32, {})
+    assert one.startswith("vd_decode_pk<") and " split" in one
+    assert many.startswith("vd_decode_pk<") and " batched" in many
+    for env in ({"VD_PK_SPLIT": "0"}, {"VD_NO_PK": "1"}):
+        one, many = names(HARD | M_B32, env)
+        assert one.startswith("vd_decode_tg<"), (env, one)
+    one, many = names(HARD | M_B32, {"VD_NO_SPLIT": "1"})
+    assert "split" not in one and "segment launch" not in one, one
+    for env in ({}, {"VD_PK_SPLIT": "0"}, {"VD_NO_SPLIT": "1"}, {"VD_NO_PK": "1"}):
+        for nm in names(SOFT16 | M_B32, env):
+            assert nm.startswith("vd_decode_tg<"), (env, nm)

@@ -16,6 +16,7 @@
 #include <vector>
 #include <algorithm>
 #include "../gpu-accelerated-viterbi-decoder_amd/csrc/vd_kernel_pk.h"
+#include "../gpu-accelerated-viterbi-decoder_amd/csrc/vd_plan.h"
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 
 int main(int argc, char** argv)
@@ -67,13 +68,16 @@ int main(int argc, char** argv)
     gs.inStride = strS;
     gh.fair = fa;
     gs.fair = fb;
-    // split single batch (vd_capi.hip launch_decode, Form::PkSplit): tail workgroups for nchunks mod SIMDs
-    const uint32_t tailc = 6400u % (4u * cus);
+    // split single batch as the library plans it (vd_plan.h plan_launch, Form::PkSplit): tail workgroups for
+    // nchunks mod SIMDs
+    const unsigned noTables[3] = {0, 0, 0};
+    const vd::LaunchPlan split = vd::plan_launch(vd::HARD, 2 * N, 1, false, vd::Knobs{}, 4 * cus, noTables);
+    if (split.form != vd::Form::PkSplit) { printf("no split launch planned\n"); return 1; }
     vd::Geom ghs = gh, gss = gs;
     ghs.nbatch = gss.nbatch = 1;
     ghs.stats = gss.stats = st;
-    ghs.tailWG = gss.tailWG = (6400u - tailc) / 4u;
-    const unsigned gsplit = ghs.tailWG + tailc;
+    ghs.tailWG = gss.tailWG = split.tailWG;
+    const unsigned gsplit = split.grid;
     hipStream_t sa, sb;
     CK(hipStreamCreateWithFlags(&sa, hipStreamNonBlocking));
     CK(hipStreamCreateWithFlags(&sb, hipStreamNonBlocking));

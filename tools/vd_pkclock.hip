@@ -14,6 +14,7 @@
 #include <map>
 #include <algorithm>
 #include "build/abl/vd_kernel_pk.h"  // the product kernel + tools-only ablation bits (tools/abl/gen_abl.py)
+#include "vd_plan.h"
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 using KFn = void (*)(const void*, void*, vd::Geom);
 
@@ -72,6 +73,12 @@ int main(int argc, char** argv)
     CK(hipMemset(g.fair, 0xFF, vd::kFairBoardWords * 4));
     uint32_t* stats;
     CK(hipMalloc(&stats, 4));
+    // the split launches' grid and tail workgroups as the library plans them (vd_plan.h), segment tables aside
+    int cus = 0;
+    CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+    const unsigned noTables[3] = {0, 0, 0};
+    const vd::LaunchPlan split = vd::plan_launch(vd::HARD, 2 * N, 1, false, vd::Knobs{}, 4 * cus, noTables);
+    if (split.form != vd::Form::PkSplit) { printf("no split launch planned\n"); return 1; }
     int rate_khz = 0;
     CK(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, 0));
     const double us_per_tick = 1000.0 / rate_khz;
@@ -114,8 +121,8 @@ int main(int argc, char** argv)
         unsigned grid;
         if (c.split) {
             gg.stats = stats;
-            gg.tailWG = (6400u - 256u) / 4u;
-            grid = gg.tailWG + 256u;
+            gg.tailWG = split.tailWG;
+            grid = split.grid;
         } else {
             gg.nbatch = K;
             gg.inStride = c.istr;
@@ -240,8 +247,8 @@ int main(int argc, char** argv)
     std::vector<std::vector<float>> ah(na), as(na);
     vd::Geom gs = g;
     gs.stats = stats;
-    gs.tailWG = (6400u - 256u) / 4u;
-    const unsigned sgrid = gs.tailWG + 256u;
+    gs.tailWG = split.tailWG;
+    const unsigned sgrid = split.grid;
     for (int r = 0; r < 3 * reps + 1; r++)
         for (int vi = 0; vi < na; vi++) {
             const int v = (vi + r) % na;
