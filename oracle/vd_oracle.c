@@ -393,6 +393,102 @@ int vo_decode_ex(int opt, const void* in, void* out, size_t inputNum, int nchunk
     return bad == 2 ? -3 : (bad ? 1 : 0);
 }
 
+/*
+ * Metric vectors at block ends (for the split launches' re-decode predictor, tests/split_predict.py).
+ * Job j = (chunk, first block, block count): the add-compare-select recursion (max only: no tie rule, no
+ * traceback, no normalisation schedule) over blocks first .. first + count - 1 of 32 stages each, block b of
+ * chunk c starting at stage startWord(c) * bpp + 32 b, from equal metrics or, where has_start[j] is set, from
+ * start[64 j ..].  After each block the 64 metrics renormalised to state 0 (pm[i] - pm[0]) are appended to
+ * `out` (64 int32 per block, jobs in order).  Equal renormalised vectors mean equal decisions from there on
+ * whatever the tie rule, which is what vd_decode_pk's split launch compares.
+ * Returns 0, or <0 on bad arguments (a job's chunk out of range).
+ */
+typedef struct {
+    const bm_src* src;
+    size_t base, rem;
+    int bpp;
+    const uint32_t* jobs;
+    const int32_t* start;
+    const uint8_t* has_start;
+    const size_t* off; /* first output block of each job */
+    int32_t* out;
+    size_t j0, j1;
+} bv_arg;
+
+static void* bv_worker(void* p)
+{
+    bv_arg* a = (bv_arg*)p;
+    for (size_t j = a->j0; j < a->j1; j++) {
+        size_t c = a->jobs[3 * j], b0 = a->jobs[3 * j + 1], nb = a->jobs[3 * j + 2];
+        size_t startWord = a->base * c + (c < a->rem ? c : a->rem);
+        size_t g = startWord * (size_t)a->bpp + 32 * b0;
+        long long pm[64], pn[64];
+        for (int i = 0; i < 64; i++) pm[i] = a->has_start && a->has_start[j] ? a->start[64 * j + (size_t)i] : 0;
+        int32_t* o = a->out + 64 * a->off[j];
+        for (size_t b = 0; b < nb; b++) {
+            for (int t = 0; t < 32; t++, g++) {
+                int A, B;
+                bm_at(a->src, g, &A, &B);
+                long long bm[4] = { -A, -B, B, A };
+                for (int T = 0; T < 64; T++) {
+                    long long c0 = pm[tabO[T][0]] + bm[tabL[T][0]];
+                    long long c1 = pm[tabO[T][1]] + bm[tabL[T][1]];
+                    pn[T] = c1 > c0 ? c1 : c0;
+                }
+                memcpy(pm, pn, sizeof(pm));
+            }
+            for (int i = 63; i >= 0; i--) pm[i] -= pm[0];
+            for (int i = 0; i < 64; i++) o[64 * b + (size_t)i] = (int32_t)pm[i];
+        }
+    }
+    return NULL;
+}
+
+int vo_block_vectors(int opt, const void* in, size_t inputNum, int nchunks, size_t njobs, const uint32_t* jobs,
+                     const int32_t* start, const uint8_t* has_start, int32_t* out, int nthreads)
+{
+    if (!vo_options_valid(opt)) return -1;
+    if (inputNum / 2 < EXTRA_L + EXTRA_R) return -2;
+    if (nchunks <= 0) nchunks = NCHUNKS_REF;
+    if (nthreads <= 0) nthreads = 1;
+    if (nthreads > 64) nthreads = 64;
+    if (has_start && !start) return -4;
+    for (size_t j = 0; j < njobs; j++) if (jobs[3 * j] >= (uint32_t)nchunks) return -5;
+    if (njobs == 0) return 0;
+    init_tabs();
+    bm_src src;
+    src.ch = CH(opt);
+    src.w = (const uint32_t*)in;
+    src.f = (const float*)in;
+    src.nstages = inputNum / 2;
+    if (CH(opt) == CH_HARD) { size_t nw = vo_input_size(opt, inputNum) / 4; if (src.nstages > nw * 16) src.nstages = nw * 16; }
+    int bpp = bits_per_pack(opt);
+    size_t packNum = vo_message_len(opt, inputNum) / (size_t)bpp;
+    size_t* off = (size_t*)malloc(njobs * sizeof(size_t));
+    if (!off) return -3;
+    size_t tot = 0;
+    for (size_t j = 0; j < njobs; j++) { off[j] = tot; tot += jobs[3 * j + 2]; }
+    pthread_t th[64];
+    bv_arg args[64];
+    /* jobs split by output blocks, so the threads get equal work */
+    int nt = 0;
+    size_t j = 0;
+    for (int i = 0; i < nthreads && j < njobs; i++) {
+        size_t want = tot * (size_t)(i + 1) / (size_t)nthreads, j0 = j;
+        while (j < njobs && (off[j] + jobs[3 * j + 2] <= want || j == j0)) j++;
+        if (i == nthreads - 1) j = njobs;
+        bv_arg a = { &src, packNum / (size_t)nchunks, packNum % (size_t)nchunks, bpp, jobs, start, has_start, off, out, j0, j };
+        args[nt++] = a;
+    }
+    if (nt == 1) bv_worker(&args[0]);
+    else {
+        for (int i = 0; i < nt; i++) pthread_create(&th[i], NULL, bv_worker, &args[i]);
+        for (int i = 0; i < nt; i++) pthread_join(th[i], NULL);
+    }
+    free(off);
+    return 0;
+}
+
 /* ---- harness restatement (viterbiDF.h:20-167, main.cpp:131-137) ---- */
 
 typedef struct { uint32_t mt[624]; int idx; } mt19937_t;

@@ -46,6 +46,8 @@ def lib():
         L.vo_ben.argtypes = [ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_void_p, sz]
         L.vo_pack.argtypes = [ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_float, ctypes.c_void_p]
         L.vo_ben.restype = ctypes.c_longlong
+        L.vo_block_vectors.argtypes = [ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_int, sz, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.vo_gen_bits.argtypes = [ctypes.c_uint32, sz, ctypes.c_void_p]
         L.vo_gen_normals.argtypes = [ctypes.c_uint32, ctypes.c_float, sz, ctypes.c_void_p]
         L.vo_mt_raw.argtypes = [ctypes.c_uint32, sz, sz, ctypes.c_void_p]
@@ -125,6 +127,51 @@ def decode(opt, packed, input_num=None, nchunks=6400, b16_policy=0, nthreads=Non
     rc = lib().vo_decode(opt, packed.ctypes.data, out.ctypes.data, input_num, nchunks, b16_policy, nthreads)
     assert rc >= 0, rc
     return out, rc == 0
+
+
+def block_vectors(opt, packed, input_num, jobs, nchunks=6400, nthreads=None):
+    """Metric vectors, renormalised to state 0, after each 32-stage block of a list of decodes (vo_block_vectors).
+
+    jobs: (chunk, first block, block count, start vector or None) each; block b of chunk c starts at stage
+    startWord(c) * bitsPerPack + 32 b; None starts from equal metrics.  Max only: no tie rule, no traceback.
+    Returns one int32 array [block count, 64] per job."""
+    jobs = list(jobs)
+    j3 = np.array([[c, b0, nb] for c, b0, nb, _ in jobs], dtype=np.uint32).reshape(-1, 3)
+    has = np.array([v is not None for _, _, _, v in jobs], dtype=np.uint8)
+    start = np.zeros((len(jobs), 64), dtype=np.int32)
+    for j, (_, _, _, v) in enumerate(jobs):
+        if v is not None:
+            start[j] = v
+    out, first = block_vectors_flat(opt, packed, input_num, j3, start, has, nchunks, nthreads)
+    return [out[f:f + n] for f, n in zip(first, j3[:, 2].astype(np.int64))]
+
+
+def block_vectors_flat(opt, packed, input_num, jobs, start=None, has_start=None, nchunks=6400, nthreads=None):
+    """block_vectors on arrays: jobs uint32 [n, 3] (chunk, first block, block count), start int32 [n, 64] and
+    has_start uint8 [n] (or None: every job from equal metrics).  Returns (vectors int32 [blocks, 64] of all
+    jobs in order, first row of each job)."""
+    _c_buffer(packed, "block_vectors")
+    need = input_size(opt, input_num)
+    if packed.nbytes < need:
+        raise ValueError(f"block_vectors: the input holds {packed.nbytes} bytes, option 0x{opt:x} with inputNum "
+                         f"{input_num} reads {need}")
+    j3 = np.ascontiguousarray(jobs, dtype=np.uint32).reshape(-1, 3)
+    n = j3.shape[0]
+    if has_start is not None:
+        has_start = np.ascontiguousarray(has_start, dtype=np.uint8)
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        if has_start.shape != (n,) or start.shape != (n, 64):
+            raise ValueError("block_vectors: start must be [jobs, 64] and has_start [jobs]")
+    counts = j3[:, 2].astype(np.int64)
+    first = np.cumsum(counts) - counts
+    out = np.zeros((int(counts.sum()), 64), dtype=np.int32)
+    if nthreads is None:
+        nthreads = min(8, os.cpu_count() or 1)
+    rc = lib().vo_block_vectors(opt, packed.ctypes.data, input_num, nchunks, n, j3.ctypes.data,
+                                start.ctypes.data if has_start is not None else None,
+                                has_start.ctypes.data if has_start is not None else None, out.ctypes.data, nthreads)
+    assert rc == 0, rc
+    return out, first
 
 
 def pack(opt, values, scale=40000.0, input_num=None):

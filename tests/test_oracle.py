@@ -158,3 +158,53 @@ def test_short_buffers_raise(vo):
     assert vo.pack(opt, vals, 40000.0, input_num=n).nbytes == vo.input_size(opt, n)
     with pytest.raises(ValueError, match="inputNum"):
         vo.pack(opt, vals[:n // 2], 40000.0, input_num=n)
+
+
+def _random_hard(seed, nbits):
+    return np.random.default_rng(seed).integers(0, 2 ** 32, (2 * nbits + 31) // 32, dtype=np.uint64).astype(np.uint32).view(np.int32)
+
+
+@pytest.mark.parametrize("kind", ["soft8-noisy", "hard-random"])
+def test_block_vectors_match_the_split_model(vo, kind):
+    """vo_block_vectors (metric vectors renormalised to state 0 after each 32-stage block: max only, no tie rule)
+    equals tools/split_model.py's numpy recursion on the same stages (read from the packed words by numpy alone),
+    from equal metrics and from a given start vector, for chunks of both lengths of a ragged partition, so the
+    chunks' first stages are checked too"""
+    from split_predict import model_chunk
+    nchunks = 12
+    nbits = 32 * (20 * nchunks + 5) + 64  # 5 chunks of 21 words, 7 of 20
+    if kind == "soft8-noisy":
+        opt = vo.SOFT8 | vo.M_B16
+        bits, vals = vo.channel(nbits, 0.0, 31, 32)
+        packed = vo.pack(opt, vals, 40.0)  # (the harness's scale of 40000 would saturate every byte)
+    else:
+        opt = vo.HARD | vo.M_B32
+        packed = _random_hard(5, nbits)
+    n = 2 * nbits
+    start = np.random.default_rng(9).integers(-50, 50, 64)
+    start = tuple(int(x - start[0]) for x in start)
+    jobs = [(0, 0, 21, None), (4, 3, 9, None), (5, 0, 20, None), (11, 14, 6, None), (7, 6, 10, start), (2, 20, 1, start)]
+    got = vo.block_vectors(opt, packed, n, jobs, nchunks=nchunks, nthreads=3)
+    assert len(got) == len(jobs)
+    for (c, b0, nb, v), g in zip(jobs, got):
+        want = np.array(model_chunk(opt, packed, nbits, nchunks, c).run(v if v is not None else (0,) * 64, b0, b0 + nb))
+        assert g.shape == (nb, 64) and g.dtype == np.int32
+        assert np.array_equal(g, want), (kind, c, b0)
+        assert (g[:, 0] == 0).all()
+    assert len({tuple(g[-1]) for g in got}) == len(jobs)  # other stages, other vectors
+    with pytest.raises(ValueError, match="reads"):
+        vo.block_vectors(opt, packed[:packed.size // 2], n, jobs, nchunks=nchunks)
+
+
+def test_block_vectors_o_b16_chunk_starts(vo):
+    """O_B16: a chunk's first stage is startWord * 16 with startWord in 16-bit words, block b 32 b stages on"""
+    from split_predict import model_chunk
+    nchunks = 6
+    nbits = 16 * (41 * nchunks + 3) + 64  # 3 chunks of 42 16-bit words, 3 of 41
+    opt = vo.HARD | vo.M_B32 | vo.O_B16
+    packed = _random_hard(6, nbits)
+    for c, b0, nb in ((0, 0, 5), (2, 1, 4), (3, 0, 6), (5, 9, 10)):
+        got, = vo.block_vectors(opt, packed, 2 * nbits, [(c, b0, nb, None)], nchunks=nchunks)
+        assert np.array_equal(got, np.array(model_chunk(opt, packed, nbits, nchunks, c).run((0,) * 64, b0, b0 + nb))), c
+
+
