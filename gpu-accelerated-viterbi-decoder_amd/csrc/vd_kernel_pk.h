@@ -29,11 +29,18 @@
 // s_sub / v_subrev (or v_xad) on the whole word (again a homomorphism).
 //
 // Batched: the two chunks of a wave are consecutive chunks 2w, 2w+1 of the launch (the same batch: 6400 is
-// even); they decode in lockstep over the longer one's blocks, each emitting only its own words.  LDS per wave
+// even); a workgroup's eight chunks (one batch: 6400 % 8 == 0) decode in lockstep over the longest one's blocks
+// (pk_wg_blocks, vd_pk_wg.h), each emitting only its own words.  LDS per wave
 // (PkLds): [ring | guard | label-region table with the +tag area (TgTabLT<true>) | guard | guard]; 6 ring slots
 // of 512 B (both chunks) in a wave's 5,120 B at 8 waves per SIMD, 7 in 5,632 B at 7 (batched SOFT8 and FP32,
-// split launches), so a traceback batch traces 5 (6) words per chunk, both chunks' words in one pass (lanes
-// 0..4 (0..5) chunk A, lanes 32.. chunk B).
+// split launches), so a traceback batch traces 5 (6) words per chunk.  A pass is the workgroup's: a VALU
+// instruction costs its issue cycles whatever the EXEC mask, and a wave tracing its own 10 (12) words paid a
+// full-width pass for a sixth of a wave of work.  So all four waves store their ring words, meet at a
+// workgroup barrier (s_waitcnt lgkmcnt(0) + s_barrier: the next group's input loads stay in flight), ONE
+// wave, taken in turn (pass count mod 4), traces the 40 (48) words of all four rings (lane l: slot l & 7 of half
+// (l >> 3) & 1 of wave l >> 4), and after a second barrier every wave moves its newest block to slot 0 and
+// goes on.  Same words, same arithmetic, a quarter of the traceback's instruction issue.  (Split launches
+// keep a pass per wave, lanes 0..5 half A, 32..37 half B: their passes are data-dependent per wave.)
 //
 // Read-out.  Every field clear is (V & ~field) | base as one v_bitop3_b32 (2 cycles; v_and_or_b32 takes 4,
 // profiles/r05/ubench12.log).
@@ -59,6 +66,7 @@
 // VALU ops: 32 dependent steps per word; tools/pk2_model.py replays the scheme against the reference).
 #pragma once
 #include "vd_kernel_tg.h"
+#include "vd_pk_wg.h"
 
 namespace vd {
 
@@ -278,6 +286,8 @@ __host__ __device__ constexpr uint32_t pk_cut(uint32_t p, uint32_t P, uint32_t W
 template <int CH, int CORE, int OB = 32, bool SPL = false, int NW = (SPL || PkFmt<CH>::P2 || (CH & 7) == FP32) ? 7 : 8>
 __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(SPL ? 7 : NW))) void vd_decode_pk(const void* __restrict__ in_all, void* __restrict__ out_all, Geom geo)
 {
+    // WG: the traceback passes are the workgroup's (header "Batched"); SPL keeps its wave-private passes
+    constexpr bool WG = !SPL;
     constexpr bool P2 = PkFmt<CH>::P2;
     constexpr int J = PkFmt<CH>::J, S = PkFmt<CH>::S;
     using IN = TgIn<CH>;
@@ -302,7 +312,11 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(SPL
     const void* const in = (const char*)in_all + batch * geo.inStride;
     char* const out = (char*)out_all + batch * geo.outStride;
     const ChunkRange crA = chunk_range(geo, cA), crB = SPL ? crA : chunk_range(geo, cA + 1);
-    if (crA.words == 0 && crB.words == 0) return;
+    // WG: every wave of the workgroup runs the workgroup's block count (vd_pk_wg.h), also a wave whose own
+    // chunks are shorter or empty: it decodes in lockstep and emits nothing, as the shorter half of a wave
+    // does.  Every return and break below that skips a workgroup barrier depends on this count only.
+    const uint32_t wgBlocks = WG ? pk_wg_blocks(geo, blockIdx.x, OB) : 0u;
+    if (WG ? wgBlocks == 0 : crA.words == 0 && crB.words == 0) return;
     if (geo.check && lane < 3 * kGuardWords) wlds[LL::guard(lane)] = kGuardPattern;
 
     // per-lane LDS byte offsets of this position's entries per phase (vd_decode_tg's INT table)
@@ -363,25 +377,33 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(SPL
         ckB = kminB + 2u;
     }
     uint64_t startA = stA + 32ull * oA, startB = stB + 32ull * oB;
-    uint32_t nblk = (kmaxA > kmaxB ? kmaxA : kmaxB) + 2;
+    uint32_t nblk = WG ? wgBlocks : (kmaxA > kmaxB ? kmaxA : kmaxB) + 2;
     uint32_t V = VBASE;
     // SPL: kept vectors, one per half: sv1 = (A's end, B's start), sv2 = (A's start, B's end) (low, high);
     // cpv[m]: the halves' vectors at checkpoint m + 1
     uint32_t sv1 = 0, sv2 = 0;
     uint32_t cpv[kPkChk > 0 ? kPkChk : 1] = {};
     uint32_t kb = 0;
-    uint32_t tbn = LL::TBS - (blockIdx.x & 3u) % LL::TBS;  // staggered first traceback batches
+    uint32_t npass = 0;                                    // WG: traceback passes so far (the tracing wave rotates)
+    uint32_t tbn = pk_first_tbn(blockIdx.x, LL::TBS);      // staggered first traceback batches
     __amdgpu_buffer_rsrc_t rsA = tg_rsrc<CH>(in, startA, availB), rsB = tg_rsrc<CH>(in, startB, availB);
     typename IN::raw_t rAA = IN::template load<0>(rsA, vo1), rBA = IN::template load<0>(rsA, vo2);
     typename IN::raw_t rAB = IN::template load<0>(rsB, vo1), rBB = IN::template load<0>(rsB, vo2);
-    // traceback roles: lanes 0..31 trace half A's words, 32..63 half B's
-    const bool tbB = lane >= 32;
-    const uint32_t tbl = (uint32_t)(lane & 31);
-    const uint64_t tbStart = tbB ? crB.startWord : crA.startWord;
-    const uint32_t tbWords = tbB ? crB.words : crA.words;
+    // traceback roles.  SPL: lanes 0..31 trace the wave's half A's words, 32..63 half B's.  WG: the tracing
+    // wave's lane l traces slot l & 7 of half (l >> 3) & 1 of wave l >> 4 (pk_trace_role); every wave keeps
+    // these constants, since the waves take the passes in turn
+    const PkTraceRole role = pk_trace_role((uint32_t)lane);
+    const bool tbB = WG ? role.half != 0u : lane >= 32;
+    const uint32_t tbl = WG ? role.slot : (uint32_t)(lane & 31);
+    const ChunkRange crT = WG ? chunk_range(geo, cA - 2u * (uint32_t)wv + 2u * role.wave + role.half) : tbB ? crB : crA;
+    const uint64_t tbStart = crT.startWord;
+    const uint32_t tbWords = crT.words;
+    // the local words the lane's chunk emits (SPL: the halves' kmin / kmax, which change from pass to pass)
+    const uint32_t tbKmax = pk_words32(tbWords, OB);
     // RF: the lane's emit-slot LDS address (chunk B: the odd bytes (HARD) / the high half of each word (SOFT8) /
     // the slot's second 64 words (SOFT4, FP32))
-    const uint32_t tbA2 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)ringA +
+    const uint32_t* const ringT = WG ? lds + role.wave * LL::WAVE + LL::RING_OFF : ringA;
+    const uint32_t tbA2 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)(const char*)ringT +
                           512u * tbl + (tbB ? (P2 ? 2u : J == 8 ? 1u : 256u) : 0u);
     // RF: the lane's phase constants for kb = 0 in bytes 0..2 of two words; a pass rotates them by kb % 3 (one
     // v_perm_b32 each with a wave-uniform selector) instead of deriving them from k % 3 per lane.
@@ -574,11 +596,23 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(SPL
             ringA[(j - 1 - kb) * 128 + ridx] = wA;
             ringA[(j - 1 - kb) * 128 + 64 + ridx] = wB;
         }
-        if (j >= 2 && (j - 1 - kb == tbn || j == nblk - 1)) {
-            wave_sync();
+        if (pk_pass_at(j, kb, tbn, nblk)) {
+            // WG: j, kb, tbn and nblk are the same in every wave of the workgroup (vd_pk_wg.h), so all four
+            // reach both barriers of every pass.  The rings are complete after the first one; one wave, taken
+            // in turn so that the four SIMDs share the work, traces every ring's words; the second one keeps
+            // the rings as they are until it has read them.
+            bool tracer = true;
+            if constexpr (WG) {
+                wg_sync_lds();
+                tracer = (uint32_t)wv == npass % kWaves;
+            } else {
+                wave_sync();
+            }
             const uint32_t nw = j - 1 - kb;
             const uint32_t k = kb + tbl;
-            if (tbl < nw && k >= (tbB ? kminB : kminA) && k < (tbB ? kmaxB : kmaxA)) {
+            const uint32_t tkmin = WG ? 0u : tbB ? kminB : kminA, tkmax = WG ? tbKmax : tbB ? kmaxB : kmaxA;
+            if (tracer)  // (wave-uniform: a scalar branch)
+            if (tbl < nw && k >= tkmin && k < tkmax) {
                 uint32_t w;
                 const uint32_t r3 = kb % 3u;  // wave-uniform
                 const uint32_t PA = rot3(phA, r3);
@@ -614,7 +648,12 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(SPL
                     if (2 * kc + 1 < tbWords) o[2 * kc + 1] = (uint16_t)(w & 0xFFFFu);
                 }
             }
-            wave_sync();
+            if constexpr (WG) {
+                wg_sync_lds();
+                npass++;
+            } else {
+                wave_sync();
+            }
             // block j becomes slot 0 of the next batch
             ringA[ridx] = wA;
             ringA[64 + ridx] = wB;
@@ -800,7 +839,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(SPL
         startA = stA + 32ull * oA;
         startB = stB + 32ull * oB;
         kb = 0;
-        tbn = LL::TBS - (blockIdx.x & 3u) % LL::TBS;
+        tbn = pk_first_tbn(blockIdx.x, LL::TBS);
         wave_sync();
         rsA = tg_rsrc<CH>(in, startA, availB);
         rsB = tg_rsrc<CH>(in, startB, availB);

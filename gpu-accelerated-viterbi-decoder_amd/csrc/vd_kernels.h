@@ -100,7 +100,7 @@ struct ChunkRange {
     uint64_t startWord;  // first output word (bpp units)
     uint32_t words;      // output words of this chunk
 };
-__device__ __forceinline__ ChunkRange chunk_range(const Geom& g, uint32_t c)
+__host__ __device__ __forceinline__ ChunkRange chunk_range(const Geom& g, uint32_t c)
 {
     ChunkRange r;
     if (c >= g.nchunks) { r.startWord = 0; r.words = 0; return r; }
@@ -112,16 +112,27 @@ __device__ __forceinline__ ChunkRange chunk_range(const Geom& g, uint32_t c)
 
 
 // Workgroups of kWaves waves (one chunk each): gfx950 admits a bounded number of workgroups per CU, so
-// single-wave workgroups could not keep all 6400 chunks resident at once.  The waves of a whole-chunk
-// workgroup never synchronise with each other (only the pieces of a split chunk do, vd_kernel_tg.h);
-// LDS is partitioned per wave and wave_sync() only orders the wave's own LDS traffic (LDS instructions
-// of one wave execute in order).
+// single-wave workgroups could not keep all 6400 chunks resident at once.  LDS is partitioned per wave and
+// wave_sync() only orders the wave's own LDS traffic (LDS instructions of one wave execute in order).  The
+// waves of a workgroup synchronise with each other in three places only: the pieces of a split chunk
+// (vd_kernel_tg.h), the tail workgroups of vd_decode_pk's split launches, and the traceback passes of
+// vd_decode_pk's batched launches, where one wave traces the words of all four rings between two workgroup
+// barriers (wg_sync_lds(), vd_kernel_pk.h "Batched"; every wave of the workgroup runs the same number of
+// blocks and passes, vd_pk_wg.h).
 constexpr int kWaves = 4;
 __device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// Workgroup barrier that orders LDS traffic only: s_waitcnt lgkmcnt(0) and the raw s_barrier.  Global loads
+// stay in flight across it (__syncthreads() would also wait for vmcnt(0)).
+__device__ __forceinline__ void wg_sync_lds()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
 }
 
 __device__ __forceinline__ uint32_t simd_slot()

@@ -78,7 +78,7 @@ PK = [
      "    // kAblClock (tools/vd_pkclock): s_memrealtime at the start, after the first pass and at the end\n"
      "    const uint64_t t_rt0 = (ABL & kAblClock) ? __builtin_amdgcn_s_memrealtime() : 0;\n"
      "    uint64_t t_rtp = 0;\n"
-     "    uint32_t npass = 0;\n"),
+     "    uint32_t t_npass = 0;\n"),
     ("    fair.begin(batch + 1 < geo.nbatch ? nullptr : geo.fair, lane);",
      "    fair.begin(batch + 1 < geo.nbatch && !(ABL & kAblFairAll) ? nullptr : geo.fair, lane);"),
     ("    uint32_t cpv[kPkChk > 0 ? kPkChk : 1] = {};\n    uint32_t kb = 0;\n",
@@ -91,8 +91,9 @@ PK = [
      "            if constexpr (Q <= 3 || (ABL & kAblNoLdsX)) pk_stage_dpp<(Q <= 3 ? Q : 0)>(V, m);"),
     ("            if constexpr (i % J == J - 1) {\n                // field read-out, both chunks",
      "            if constexpr (i % J == J - 1 && !(ABL & kAblNoReadout)) {\n                // field read-out, both chunks"),
-    ("            if (tbl < nw && k >= (tbB ? kminB : kminA) && k < (tbB ? kmaxB : kmaxA)) {",
-     "            if (!(ABL & kAblNoTraceback) && tbl < nw && k >= (tbB ? kminB : kminA) && k < (tbB ? kmaxB : kmaxA)) {"),
+    # (batched launches keep the two workgroup barriers of a pass: kAblNoTraceback removes the tracing only)
+    ("            if (tbl < nw && k >= tkmin && k < tkmax) {",
+     "            if (!(ABL & kAblNoTraceback) && tbl < nw && k >= tkmin && k < tkmax) {"),
     ("                if constexpr (OB == 32) {\n                    ((uint32_t*)out)[tbStart + kc] = w;",
      "                if constexpr (ABL & kAblNoStores) {\n                    sink ^= w + kc;\n"
      "                } else if constexpr (OB == 32) {\n                    ((uint32_t*)out)[tbStart + kc] = w;"),
@@ -105,7 +106,7 @@ PK = [
      "            if constexpr (!(ABL & kAblNoFair))\n                if (!(ABL & kAblFair2) || (j / 3) % 2 == 0) fair.group(j, 3u, lane);\n"),
     ("        if constexpr (!SPL) break;\n",
      "        if constexpr ((ABL & kAblClock) != 0) {\n            if (pass == 0) t_rtp = __builtin_amdgcn_s_memrealtime();\n"
-     "            npass = pass + 1u;\n        }\n        if constexpr (!SPL) break;\n"),
+     "            t_npass = pass + 1u;\n        }\n        if constexpr (!SPL) break;\n"),
     ("    fair.end(lane);\n    if (geo.check) {",
      "    fair.end(lane);\n"
      "    if constexpr ((ABL & kAblClock) != 0) {  // 8 words per wave behind the outputs (at least 16 MiB in)\n"
@@ -118,7 +119,7 @@ PK = [
      "            d[2] = t1;\n"
      "            d[3] = (uint32_t)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));   // HW_ID\n"
      "            d[4] = (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));  // XCC_ID\n"
-     "            d[5] = npass;\n"
+     "            d[5] = t_npass;\n"
      "        }\n    }\n"
      "    if constexpr ((ABL & kAblNoStores) != 0) {\n"
      "        if (sink == 0x9E3779B9u) ((uint32_t*)out)[lane] = sink;  // keeps the traceback live\n"
