@@ -164,22 +164,26 @@ static DeviceState* device_state(int device)
     return st[device];
 }
 // Which kernel, launch form and grid a decode takes: vd_plan.h, for this decoder's knobs and device
-static LaunchPlan plan_of(const vd_decoder* d, size_t inputNum, uint32_t nbatch, bool llr)
+// (punct: a punctured decode, planned on vd_decode_tg's forms only)
+static LaunchPlan plan_of(const vd_decoder* d, size_t inputNum, uint32_t nbatch, bool llr, bool punct = false)
 {
-    return plan_launch(d->options, inputNum, nbatch, llr, d->knobs, d->ds->nsimd, d->ds->segWG);
+    return plan_launch(d->options, inputNum, nbatch, llr, punct ? punct_knobs(d->knobs) : d->knobs, d->ds->nsimd,
+                       d->ds->segWG);
 }
 
 // llr: in_d holds inputNum float channel values, quantised in the kernel (scale = packer scale).
 // nbatch > 1: batch b at in_d + b * inStride, out_d + b * outStride, all in one launch (never split).
+// pun: in_d holds the kept float values of a punctured stream (llr set; vd_punct.h), inputNum the mother-code values.
 // *form: the launch form taken (the blocking entry points' split-cap check wants it)
 static int launch_decode(const vd_decoder* d, const void* in_d, void* out_d, size_t inputNum, hipStream_t s,
                          Form* form = nullptr, bool llr = false, float scale = 1.0f, uint32_t nbatch = 1,
-                         uint64_t inStride = 0, uint64_t outStride = 0)
+                         uint64_t inStride = 0, uint64_t outStride = 0, const Punct* pun = nullptr)
 {
     const int options = d->options;
-    const LaunchPlan p = plan_of(d, inputNum, nbatch, llr);
+    const LaunchPlan p = plan_of(d, inputNum, nbatch, llr, pun != nullptr);
     if (form) *form = p.form;
-    launch_fn f = launcher<Launch>(p.form, llr, ch_of(options), met_of(options), out_of(options) == 1);
+    launch_fn f = pun ? launcher_punct<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
+                      : launcher<Launch>(p.form, llr, ch_of(options), met_of(options), out_of(options) == 1);
     if (!f) return fail(VD_ERR_OPTIONS, "invalid options");
     if (!p.launches) return VD_OK;
     // the launch goes to the stream's device (the null stream: the current device); the board and the
@@ -201,6 +205,10 @@ static int launch_decode(const vd_decoder* d, const void* in_d, void* out_d, siz
     g.inStride = inStride;
     g.outStride = outStride;
     g.tailWG = p.tailWG;
+    if (pun) {
+        g.pun = *pun;
+        g.punBytes = punct_len(*pun, inputNum) * sizeof(float);
+    }
     if (p.seg != kSegNone) g.seg = d->ds->seg[p.seg];
     if (p.stats) g.stats = d->ds->stats;
     f(in_d, out_d, g, p.grid, s);
@@ -251,7 +259,8 @@ const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, i
 {
     static thread_local std::string name;
     if (!d || nbatch < 1) return "-";
-    name = plan_name(plan_of(d, inputNum, (uint32_t)nbatch, llr != 0), d->options, llr != 0);
+    if (llr == 2 && ch_of(d->options) == HARD) return "-";  // no punctured HARD kernels
+    name = plan_name(plan_of(d, inputNum, (uint32_t)nbatch, llr != 0, llr == 2), d->options, llr == 2 ? 2 : llr != 0);
     return name.c_str();
 }
 
@@ -334,12 +343,12 @@ static int check_split_cap(const vd_decoder* d, Form form)
 // the blocking decode through the decoder's device buffers: in_h to in_d, the launch between the timing
 // events, out_d to out_h, kernel-only time
 static int run_staged(vd_decoder* d, void* in_d, const void* in_h, size_t inB, void* out_h, size_t outB, size_t inputNum,
-                      bool llr, float scale, float* kernel_ms)
+                      bool llr, float scale, float* kernel_ms, const Punct* pun = nullptr)
 {
     Form form = Form::Tg;
     VD_HIP(hipMemcpyAsync(in_d, in_h, inB, hipMemcpyHostToDevice, d->stream));
     VD_HIP(hipEventRecord(d->ev0, d->stream));
-    int rc = launch_decode(d, in_d, d->out_d, inputNum, d->stream, &form, llr, scale);
+    int rc = launch_decode(d, in_d, d->out_d, inputNum, d->stream, &form, llr, scale, 1, 0, 0, pun);
     if (rc != VD_OK) return rc;
     VD_HIP(hipEventRecord(d->ev1, d->stream));
     VD_HIP(hipMemcpyAsync(out_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
@@ -406,7 +415,7 @@ int vd_guard_violations(vd_decoder* d, uint64_t* count)
 // in_stride: any multiple of its alignment (0 = every batch decodes the same input); inputs are only read,
 // so overlapping windows (e.g. sliding) are valid
 static int run_device(vd_decoder* d, const void* in_d, void* out_d, size_t inputNum, void* stream, bool llr, float scale,
-                      int nbatch, size_t in_stride, size_t output_stride)
+                      int nbatch, size_t in_stride, size_t output_stride, const Punct* pun = nullptr)
 {
     if (!d || !in_d || !out_d) return fail(VD_ERR_ARG, "null argument");
     if (nbatch < 1) return fail(VD_ERR_ARG, "nbatch must be >= 1");
@@ -414,10 +423,13 @@ static int run_device(vd_decoder* d, const void* in_d, void* out_d, size_t input
     if (nbatch > 1 && output_stride < message_len(d->options, inputNum) / 8)
         return fail(VD_ERR_ARG, "output_stride smaller than the output size: batches would overlap");
     if ((uint64_t)vd::kChunks * (uint64_t)nbatch > 0xFFFFFFFFull) return fail(VD_ERR_ARG, "nbatch too large");
-    if (llr && ((in_stride & 15) || (output_stride & 3))) return fail(VD_ERR_ARG, "llr_stride % 16 or output_stride % 4 != 0");
+    // punctured input is read by single-dword loads: 4-byte alignment, of the pointer too
+    if (pun && (((uintptr_t)in_d | in_stride | output_stride) & 3))
+        return fail(VD_ERR_ARG, "rx_d, rx_stride and output_stride must be multiples of 4 bytes");
+    if (llr && !pun && ((in_stride & 15) || (output_stride & 3))) return fail(VD_ERR_ARG, "llr_stride % 16 or output_stride % 4 != 0");
     if (!llr && ((in_stride | output_stride) & 3)) return fail(VD_ERR_ARG, "strides must be multiples of 4 bytes");
     return launch_decode(d, in_d, out_d, inputNum, (hipStream_t)stream, nullptr, llr, scale, (uint32_t)nbatch, in_stride,
-                         output_stride);
+                         output_stride, pun);
 }
 
 int vd_run_device(vd_decoder* d, const void* input_d, void* output_d, size_t inputNum, void* stream)
@@ -475,6 +487,59 @@ int vd_run_llr(vd_decoder* d, const float* llr_h, void* output_h, size_t inputNu
     if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
     if (rc != VD_OK) return rc;
     return run_staged(d, d->llr_d, llr_h, inB, output_h, outB, inputNum, true, scale, kernel_ms);
+}
+
+// ---- punctured streams (vd_punct.h; vd_decode_tg<PUN+...>) ----
+// the pattern and the decoder of a punctured decode: VD_ERR_ARG / VD_ERR_OPTIONS, or *pn filled in
+static int punct_args(const vd_decoder* d, int period, uint32_t keep0, uint32_t keep1, size_t inputNum, Punct* pn)
+{
+    if (!d) return fail(VD_ERR_ARG, "null argument");
+    if (!punct_valid(period, keep0, keep1))
+        return fail(VD_ERR_ARG, "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, "
+                                "at least one bit set");
+    if (ch_of(d->options) == HARD)
+        return fail(VD_ERR_OPTIONS, "punctured input on a HARD decoder: a punctured value must decode as code 0 = value 0, "
+                                    "and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");
+    if (inputNum / 2 > kPunctMaxStages) return fail(VD_ERR_ARG, "inputNum too large: punctured decodes index stages in 32 bits");
+    *pn = punct_make(period, keep0, keep1);
+    return VD_OK;
+}
+
+size_t vd_punctured_len(int period, uint32_t keep0, uint32_t keep1, size_t inputNum)
+{
+    return punct_valid(period, keep0, keep1) ? (size_t)punct_len(punct_make(period, keep0, keep1), inputNum) : 0;
+}
+
+int vd_run_device_punct_batch(vd_decoder* d, const float* rx_d, size_t rx_stride, void* output_d, size_t output_stride,
+                              size_t inputNum, float scale, int period, uint32_t keep0, uint32_t keep1, int nbatch,
+                              void* stream)
+{
+    Punct pn;
+    int rc = punct_args(d, period, keep0, keep1, inputNum, &pn);
+    if (rc != VD_OK) return rc;
+    return run_device(d, rx_d, output_d, inputNum, stream, true, scale, nbatch, rx_stride, output_stride, &pn);
+}
+
+int vd_run_device_punct(vd_decoder* d, const float* rx_d, void* output_d, size_t inputNum, float scale, int period,
+                        uint32_t keep0, uint32_t keep1, void* stream)
+{
+    return vd_run_device_punct_batch(d, rx_d, 0, output_d, 0, inputNum, scale, period, keep0, keep1, 1, stream);
+}
+
+int vd_run_punct(vd_decoder* d, const float* rx_h, void* output_h, size_t inputNum, float scale, int period, uint32_t keep0,
+                 uint32_t keep1, float* kernel_ms)
+{
+    Punct pn;
+    int rc = punct_args(d, period, keep0, keep1, inputNum, &pn);
+    if (rc != VD_OK) return rc;
+    if (!rx_h || !output_h) return fail(VD_ERR_ARG, "null argument");
+    if (message_len(d->options, inputNum) == 0) return fail(VD_ERR_ARG, "inputNum too small");
+    const size_t inB = (size_t)punct_len(pn, inputNum) * sizeof(float), outB = message_len(d->options, inputNum) / 8;
+    VD_HIP(hipSetDevice(d->device));
+    rc = grow(d->llr_d, d->cap_llr, inB);
+    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
+    if (rc != VD_OK) return rc;
+    return run_staged(d, d->llr_d, rx_h, inB, output_h, outB, inputNum, true, scale, kernel_ms, &pn);
 }
 
 void* vd_host_alloc(size_t bytes)

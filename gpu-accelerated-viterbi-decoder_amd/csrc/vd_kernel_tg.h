@@ -40,6 +40,9 @@ namespace vd {
 // channel ids: HARD..FP32 = packed input (viterbiBM.cuh formats); 8 + base = float channel values
 // quantised on the fly exactly like SoftDecisionPacker(base, scale) would have packed them (vd_pack.h)
 constexpr int kLlr = 8;
+// 16 + base = float channel values of a punctured stream (SOFT4 .. FP32): the kept values only, found through
+// the pattern's index map in the loads that feed the table build and quantised like kLlr + base (TgInPun)
+constexpr int kPun = 16;
 
 template <int CH>
 struct TgFmt {
@@ -592,6 +595,64 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tg_rsrc(const void* in, uint64
     return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)in + ((uint64_t)oh << 32 | ol)), (short)0, (int)lo, 0x00020000);
 }
 
+// ---------------------------------------------------------------- punctured float input (vd_punct.h)
+// The received buffer holds only the kept values, so where a stage's two floats lie depends on the stage
+// modulo the pattern's period: a lane's offsets change from group to group with r0 = g0 % period (TgInLlr's
+// voff(li) is fixed).  Per group: (q0, r0) of the first stage g0 on the scalar unit (punct_divmod, the
+// reciprocal comes with the pattern in Geom), the resource based at float q0 * Kp of the batch's buffer and
+// ending at the last received value (reads past it return zero, as in tg_rsrc), and per lane the two float
+// offsets of its stage from r0 + stage-in-group (punct_rel) for two single-dword loads.
+// A punctured value must read as +0.0f.  Its lane gives the offset kPunErased = 2^31, and the range is
+// clamped to 2^31 - 1 bytes (kept lanes' offsets stay below 4 (2 (16 + 96) + 32) bytes): offset + 4 exceeds
+// every range the resource can have, with no 32-bit wrap-around, so the range check rejects the load and
+// the lane receives zero -- no flag kept in a register until the values are used a group later.
+// Everything after the loads is TgInLlr<BASE>: the same quantisation, table rows, cores and traceback.
+template <int BASE>
+struct TgInPun : TgInLlr<BASE> {
+    static_assert(BASE != HARD, "HARD has no neutral code for an erasure");
+    static constexpr bool PUN = true;
+};
+template <> struct TgIn<kPun + SOFT4> : TgInPun<SOFT4> {};
+template <> struct TgIn<kPun + SOFT8> : TgInPun<SOFT8> {};
+template <> struct TgIn<kPun + SOFT16> : TgInPun<SOFT16> {};
+template <> struct TgIn<kPun + FP32> : TgInPun<FP32> {};
+template <class T, class = void>
+struct HasPun : std::false_type {};
+template <class T>
+struct HasPun<T, std::void_t<decltype(T::PUN)>> : std::bool_constant<T::PUN> {};
+constexpr uint32_t kPunErased = 0x80000000u;
+// resource for the stages from g0 (< 2^32) of a punctured buffer of availBytes; *r0 = g0 % period
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tg_rsrc_pun(const void* in, uint64_t g0, uint64_t availBytes, const Punct& pn,
+                                                              uint32_t* r0)
+{
+    uint32_t q0;
+    punct_divmod(pn, __builtin_amdgcn_readfirstlane((uint32_t)g0), q0, *r0);  // uniform: scalar unit
+    q0 = __builtin_amdgcn_readfirstlane(q0);  // (keeps the 32 x 32 -> 64-bit product below off the vector unit)
+    const uint32_t k4 = pn.kp * 4u, ol = q0 * k4, oh = __umulhi(q0, k4);
+    const uint32_t al = __builtin_amdgcn_readfirstlane((uint32_t)availBytes);
+    const uint32_t ah = __builtin_amdgcn_readfirstlane((uint32_t)(availBytes >> 32));
+    uint32_t lo, hi;
+    asm("s_sub_u32 %[lo], %[al], %[ol]\n\t"
+        "s_subb_u32 %[hi], %[ah], %[oh]\n\t"  // SCC = borrow: the group starts past the data
+        "s_cselect_b32 %[lo], 0, %[lo]\n\t"
+        "s_cselect_b32 %[hi], 0, %[hi]\n\t"
+        "s_cmp_lg_u32 %[hi], 0\n\t"
+        "s_cselect_b32 %[lo], -1, %[lo]\n\t"
+        "s_min_u32 %[lo], %[lo], 0x7fffffff"
+        : [lo] "=&s"(lo), [hi] "=&s"(hi)
+        : [al] "s"(al), [ah] "s"(ah), [ol] "s"(ol), [oh] "s"(oh)
+        : "scc");
+    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)in + ((uint64_t)oh << 32 | ol)), (short)0, (int)lo, 0x00020000);
+}
+// the two values of stage g0 + s (s < 96) of the group whose resource is rs
+__device__ __forceinline__ float2 tg_pun_load(__amdgpu_buffer_rsrc_t rs, const Punct& pn, uint32_t r0, uint32_t s)
+{
+    const PunctRel e = punct_rel(pn, r0, s);
+    const uint32_t o0 = (e.i0 << 2) | ((e.has0 ^ 1u) * kPunErased), o1 = (e.i1 << 2) | ((e.has1 ^ 1u) * kPunErased);
+    const uint32_t x = __builtin_amdgcn_raw_buffer_load_b32(rs, o0, 0, 0), y = __builtin_amdgcn_raw_buffer_load_b32(rs, o1, 0, 0);
+    return make_float2(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
+}
+
 // ---------------------------------------------------------------- segment launches
 // A launch of 6400 chunks on 1024 SIMDs, one chunk per wave, puts 7 waves on a quarter of the SIMDs and
 // 6 on the rest, and the 7-wave SIMDs set the kernel time.  In a segment launch (Geom::seg) workgroup g
@@ -777,7 +838,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         for (int r = 0; r < nrun; r++) tot += seg_run(sw, b0, b1, r).words + 2;
         fscale = (1u << 20) / (tot ? tot : 1u);
     }
-    const uint64_t availB = IN::bytes(geo.availStages);
+    constexpr bool PUN = HasPun<IN>::value;  // punctured input: per-group offsets (tg_rsrc_pun, tg_pun_load)
+    const uint64_t availB = PUN ? geo.punBytes : IN::bytes(geo.availStages);
     const uint32_t vo1 = IN::voff(sA), vo2 = IN::voff(sB);
     // segment workgroups (uniform bookkeeping): bit q of `verified` = segment q checked exact (segments
     // that start at a chunk start are exact).  vS / vE: this segment's start / end vector; vIn: the vector a
@@ -808,9 +870,18 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     const uint32_t j0 = pass == 0 ? 0u : (uint32_t)Xspec;
     uint32_t kb = 0;
     uint32_t tbn = pass == 0 ? LL::TBS - 3 * (blockIdx.x & 3) : LL::TBS;
-    __amdgpu_buffer_rsrc_t rs = tg_rsrc<CH>(in, start + 32ull * j0, availB);
-    typename IN::raw_t rA = IN::template load<0>(rs, vo1);               // stage sA of the group
-    typename IN::raw_t rB = IN::template load<0>(rs, vo2);               // stage sB
+    __amdgpu_buffer_rsrc_t rs;
+    typename IN::raw_t rA, rB;  // the input of stages sA and sB of the group
+    if constexpr (PUN) {
+        uint32_t r0;
+        rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
+        rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
+        rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
+    } else {
+        rs = tg_rsrc<CH>(in, start + 32ull * j0, availB);
+        rA = IN::template load<0>(rs, vo1);
+        rB = IN::template load<0>(rs, vo2);
+    }
 
     // Branch-metric table reads, software-pipelined: the entries of stage r are loaded TGD stages
     // ahead; one ds_read_b64 at an even period also carries the entry of the stage 6 later.  The
@@ -985,6 +1056,12 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
                 put_row(P1{}, A, B, r6b);
             }
         }
+        if constexpr (PUN) {  // the next group's received values, at the offsets of its own r0
+            uint32_t r0;
+            rs = tg_rsrc_pun(in, start + 32ull * (j + 3), availB, geo.pun, &r0);
+            rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
+            rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
+        } else
         {  // the next group's input words
             rs = tg_rsrc<CH>(in, start + 32ull * (j + 3), availB);
             rA = IN::template load<0>(rs, vo1);

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility>
+#include "vd_punct.h"
 
 namespace vd {
 
@@ -62,6 +63,10 @@ struct Geom {
     // vd_decode_pk split launches: workgroups from tailWG on decode one chunk each (chunk 4 tailWG + g -
     // tailWG) with their 4 waves (vd_kernel_pk.h "split"); ~0u = none
     uint32_t tailWG = ~0u;
+    // punctured float input (channel ids kPun + format, vd_kernel_tg.h; vd_punct.h): the pattern (period 0 =
+    // none) and the bytes of received values in each batch's buffer
+    Punct pun;
+    uint64_t punBytes = 0;
 };
 // Progress board of the fairness controller: per SIMD slot (XCC, SE, SH, CU, SIMD from the hardware
 // wave id) kFairWaves 32-bit words, one per hardware wave slot of that SIMD (HW_ID.WAVE_ID): the blocks

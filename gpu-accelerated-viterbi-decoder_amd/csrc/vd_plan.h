@@ -2,7 +2,7 @@
 // the sizes, the knobs read at vd_create and the device's SIMD and segment-table counts (no HIP runtime calls,
 // no decoder: tests/cxx/plan_check.cpp checks it on the CPU), with the option helpers, the list of kernels
 // and the kernel names.  Shared by the C-ABI (vd_capi.hip) and the timing tools.
-// Include after vd_kernel_tg.h (kSplitMinWords, kLlr; the tools include their ablation copy of it).
+// Include after vd_kernel_tg.h (kSplitMinWords, kLlr, kPun; the tools include their ablation copy of it).
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -115,6 +115,30 @@ typename L::fn launcher(Form f, bool llr, int ch, int me, bool o16)
     return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[(int)f][llr][ch][me][o16] : nullptr;
 }
 
+// Punctured float input (channel ids kPun + format, vd_kernel_tg.h): vd_decode_tg only, every valid pair but
+// HARD's (an erasure has no hard code), 9 pairs x {O32, O16}.  A table of its own: launcher<L>'s holds exactly
+// the kernels of the packed and LLR plans.  Punctured decodes are planned with Knobs::pk = 0 (punct_knobs): one
+// chunk per wave, batched, or a segment launch for long single batches.
+#define VD_PUN_PAIRS(X) \
+    X(SOFT4, B32) X(SOFT4, B16) X(SOFT4, F16) X(SOFT8, B32) X(SOFT8, B16) X(SOFT16, B32) X(FP32, B32) X(FP32, B16) X(FP32, F16)
+template <class L>
+typename L::fn launcher_punct(int ch, int me, bool o16)
+{
+    struct Table {
+        typename L::fn at[5][3][2] = {};
+        Table()
+        {
+#define VD_X(C, M)                                      \
+    at[C][M][0] = &L::template tg<kPun + C, M, 32>;     \
+    at[C][M][1] = &L::template tg<kPun + C, M, 16>;
+            VD_PUN_PAIRS(VD_X)
+#undef VD_X
+        }
+    };
+    static const Table t;
+    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
+}
+
 // ---------------------------------------------------------------- the knobs (read once, at vd_create)
 struct Knobs {
     int split = 1;    // segment launches: 0 none (VD_NO_SPLIT=1), 1 pieces, 2 thirds, 3 sevenths (VD_SPLIT=...)
@@ -131,6 +155,12 @@ inline Knobs knobs_from_env()
     k.pk = is("VD_NO_PK", '1') ? 0 : 1;
     k.pksplit = is("VD_PK_SPLIT", '0') ? 0 : 1;
     k.pktail = is("VD_PK_TAIL", '0') ? 0 : 1;
+    return k;
+}
+// the knobs a punctured decode is planned with: vd_decode_tg's forms only (there are no vd_decode_pk twins)
+inline Knobs punct_knobs(Knobs k)
+{
+    k.pk = 0;
     return k;
 }
 
@@ -194,11 +224,12 @@ inline LaunchPlan plan_launch(int o, size_t inputNum, uint32_t nbatch, bool llr,
 inline constexpr const char* kChNames[5] = {"HARD", "SOFT4", "SOFT8", "SOFT16", "FP32"};
 inline constexpr const char* kCoreNames[3] = {"B32", "B16", "F16"};
 
-// vd_decoder_kernel_name: the kernel and launch form of one planned launch
-inline std::string plan_name(const LaunchPlan& p, int o, bool llr)
+// vd_decoder_kernel_name: the kernel and launch form of one planned launch; input: 0 packed words, 1 float
+// channel values (LLR), 2 punctured float values (PUN)
+inline std::string plan_name(const LaunchPlan& p, int o, int input)
 {
     if (!p.launches) return "-";
-    const std::string args = std::string(llr ? "LLR+" : "") + kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," +
+    const std::string args = std::string(input == 2 ? "PUN+" : input ? "LLR+" : "") + kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," +
                              (out_of(o) ? "O16" : "O32") + ">";
     if (p.form == Form::PkBatched) return "vd_decode_pk<" + args + " batched: two chunks per wave, int16 halves";
     if (p.form == Form::PkSplit) return "vd_decode_pk<" + args + " split: one chunk per wave cut in two, int16 halves";

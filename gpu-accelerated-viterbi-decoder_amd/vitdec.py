@@ -46,7 +46,14 @@ EXPORTS = ["vd_options_valid", "vd_input_size", "vd_message_len", "vd_output_siz
            "vd_pack_device", "vd_run_device_llr", "vd_run_llr", "vd_host_alloc", "vd_host_free",
            "vd_run_stream", "vd_channel_device", "vd_simulate_device", "vd_mt_state_after", "vd_split_redecodes",
            "vd_split_cap_exits", "vd_set_guard_check", "vd_guard_violations", "vd_run_device_llr_batch", "vd_build_info",
-           "vd_decoder_kernel_name"]
+           "vd_decoder_kernel_name", "vd_punctured_len", "vd_run_device_punct", "vd_run_device_punct_batch",
+           "vd_run_punct"]
+
+# puncture patterns (period, keep0, keep1): bit i of keep0 / keep1 = the first (0171) / second (0133) encoder
+# output of the stages t with t % period == i is transmitted.  Any valid masks decode (and equal the rate-1/2
+# decode of the depunctured stream); these three are the ones the fixed decode window is long enough for
+# (DESIGN.md "Punctured streams")
+PUNCTURE = {"1/2": (1, 1, 1), "2/3": (2, 0b01, 0b11), "3/4": (3, 0b101, 0b011)}
 
 
 class VitdecError(RuntimeError):
@@ -94,6 +101,10 @@ def lib():
            "vd_run_device_llr": ([vp, vp, vp, sz, f, vp], None),
            "vd_run_llr": ([vp, vp, vp, sz, f, ctypes.POINTER(f)], None),
            "vd_run_device_llr_batch": ([vp, vp, sz, vp, sz, sz, f, ctypes.c_int, vp], None),
+           "vd_punctured_len": ([i, ctypes.c_uint32, ctypes.c_uint32, sz], sz),
+           "vd_run_device_punct": ([vp, vp, vp, sz, f, i, ctypes.c_uint32, ctypes.c_uint32, vp], None),
+           "vd_run_device_punct_batch": ([vp, vp, sz, vp, sz, sz, f, i, ctypes.c_uint32, ctypes.c_uint32, i, vp], None),
+           "vd_run_punct": ([vp, vp, vp, sz, f, i, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(f)], None),
            "vd_kernel_name": ([i], ctypes.c_char_p),
            "vd_decoder_kernel_name": ([vp, sz, i, i], ctypes.c_char_p)}
     for name, (args, res) in sig.items():
@@ -240,8 +251,9 @@ class ViterbiCUDA:
 
     def kernel_for(self, inputNum, nbatch=1, llr=False):
         """the kernel and launch form this decoder runs for nbatch batches of inputNum values
-        (vd_decoder_kernel_name: follows VD_NO_PK / VD_PK_SPLIT / VD_NO_SPLIT as read at creation)"""
-        return lib().vd_decoder_kernel_name(self._h, inputNum, nbatch, 1 if llr else 0).decode()
+        (vd_decoder_kernel_name: follows VD_NO_PK / VD_PK_SPLIT / VD_NO_SPLIT as read at creation); llr: False /
+        0 packed input, True / 1 float channel values, 2 punctured float values"""
+        return lib().vd_decoder_kernel_name(self._h, inputNum, nbatch, int(llr)).decode()
 
     def set_guard_check(self, enable=True):
         """LDS guard words around every wave's table and ring, counted at kernel exit when overwritten
@@ -295,6 +307,39 @@ class ViterbiCUDA:
         _check(lib().vd_run_device_llr_batch(self._h, ctypes.c_void_p(llr_ptr), llr_stride, ctypes.c_void_p(output_ptr),
                                              output_stride, inputNum, scale, nbatch, ctypes.c_void_p(stream)))
 
+    # ---- punctured streams: the kept float values only, depunctured in the decode's loads ----
+    def run_punct(self, rx_h, pattern, inputNum, scale=40000.0, output_h=None):
+        """Blocking decode of a punctured stream: rx_h = puncture(values, pattern), the punctured_len(pattern,
+        inputNum) kept floats of inputNum mother-code values; pattern = (period, keep0, keep1), e.g.
+        PUNCTURE["3/4"].  Equals run_llr(depuncture(rx_h, pattern, inputNum), scale) word for word.  SOFT4,
+        SOFT8, SOFT16 and FP32 decoders (HARD: VD_ERR_OPTIONS, a hard decision has no neutral code for a
+        punctured value).  FP32 decoders need a scale like the harness's 40000: at scale 1 the truncating
+        FP32 branch metric loses a lone +-1 beside a punctured value (rate 3/4 then decodes with errors in a
+        third of the bits on a nearly noiseless stream).  Returns (out, ms)."""
+        rx_h = np.ascontiguousarray(rx_h, dtype=np.float32)
+        need = punctured_len(pattern, inputNum)  # (0: an invalid pattern, which the call below reports)
+        if rx_h.size < need:
+            raise VitdecError(f"{rx_h.size} received values given, punctured_len{pattern} of {inputNum} is {need}")
+        if output_h is None:
+            output_h = np.zeros(self.getOutputSize(inputNum) // np.dtype(self.decPack_t).itemsize,
+                                dtype=self.decPack_t)
+        ms = ctypes.c_float(0.0)
+        _check(lib().vd_run_punct(self._h, rx_h.ctypes.data, output_h.ctypes.data, inputNum, scale, *pattern,
+                                  ctypes.byref(ms)))
+        return output_h, ms.value
+
+    def run_device_punct(self, rx_ptr, output_ptr, inputNum, pattern, scale=40000.0, stream=0):
+        """Async decode of punctured_len(pattern, inputNum) device floats (4-byte aligned)."""
+        _check(lib().vd_run_device_punct(self._h, ctypes.c_void_p(rx_ptr), ctypes.c_void_p(output_ptr), inputNum, scale,
+                                         *pattern, ctypes.c_void_p(stream)))
+
+    def run_device_punct_batch(self, rx_ptr, rx_stride, output_ptr, output_stride, inputNum, nbatch, pattern,
+                               scale=40000.0, stream=0):
+        """nbatch punctured decodes in one launch: batch b at rx_ptr + b * rx_stride bytes -> output_ptr + b *
+        output_stride bytes (strides multiples of 4 bytes; vd_run_device_punct_batch)."""
+        _check(lib().vd_run_device_punct_batch(self._h, ctypes.c_void_p(rx_ptr), rx_stride, ctypes.c_void_p(output_ptr),
+                                               output_stride, inputNum, scale, *pattern, nbatch, ctypes.c_void_p(stream)))
+
 
 class PinnedArray:
     """A numpy view of page-locked host memory from vd_host_alloc (freed with the object)."""
@@ -317,6 +362,34 @@ def pack_device(options, llr_ptr, inputNum, packed_ptr, scale=40000.0, stream=0)
     """The reference's SoftDecisionPacker on device floats -> vd_input_size(options, inputNum) bytes."""
     _check(lib().vd_pack_device(options, ctypes.c_void_p(llr_ptr), inputNum, scale, ctypes.c_void_p(packed_ptr),
                                 ctypes.c_void_p(stream)))
+
+
+def punctured_len(pattern, inputNum):
+    """received values of inputNum mother-code values under pattern (vd_punctured_len; 0: invalid pattern)"""
+    return lib().vd_punctured_len(*pattern, inputNum)
+
+
+def _kept(pattern, inputNum):
+    """which of the first 2 * (inputNum // 2) mother positions pattern = (period, keep0, keep1) transmits"""
+    period, keep0, keep1 = pattern
+    r = np.arange(inputNum // 2) % period
+    return np.stack([(keep0 >> r) & 1, (keep1 >> r) & 1], axis=1).reshape(-1).astype(bool)
+
+
+def puncture(values, pattern):
+    """the kept values of a rate-1/2 stream, in mother order (host helper: the transmitter's puncturer)"""
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    kept = _kept(pattern, v.size)
+    return v[:kept.size][kept]
+
+
+def depuncture(rx, pattern, inputNum):
+    """the rate-1/2 stream of inputNum values a punctured decode is defined by: rx at the kept positions,
+    +0.0 at the punctured ones"""
+    kept = _kept(pattern, inputNum)
+    out = np.zeros(inputNum, dtype=np.float32)
+    out[:kept.size][kept] = np.asarray(rx, dtype=np.float32).reshape(-1)[:int(kept.sum())]
+    return out
 
 
 def simulate_host(options, n_bits, snr, bit_seed, noise_seed):

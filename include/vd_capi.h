@@ -130,6 +130,39 @@ int vd_run_device_llr_batch(vd_decoder* dec, const float* llr_d, size_t llr_stri
 /* Blocking host-to-host variant (H2D of the floats, fused decode, D2H); kernel_ms as in vd_run. */
 int vd_run_llr(vd_decoder* dec, const float* llr_h, void* output_h, size_t inputNum, float scale, float* kernel_ms);
 
+/* ---- punctured streams (rates 2/3, 3/4, ...; new, the reference decodes rate 1/2 only) ----
+ * A puncture pattern is (period, keep0, keep1), 1 <= period <= 16: bit i of keep0 says that the first encoder
+ * output (0171, mother index 2t) of every stage t with t % period == i was transmitted, keep1 the same for the
+ * second output (0133, mother index 2t + 1); at least one bit set, none at or above bit `period`.  E.g. rate
+ * 2/3: (2, 0x1, 0x3); rate 3/4: (3, 0x5, 0x3); (1, 1, 1) is the unpunctured stream.
+ * inputNum keeps its meaning, the number of mother-code values (2 per stage), so the size helpers above hold
+ * unchanged; the received buffer holds the kept values in mother order as floats, vd_punctured_len of them.
+ * The decode equals, word for word, vd_run_device_llr of the depunctured stream: inputNum floats, the
+ * received value at kept positions and +0.0f at punctured ones, same scale.  The depuncturing is an index
+ * map in the loads of the branch-metric table build: no expanded copy exists.  SOFT4, SOFT8, SOFT16 and FP32
+ * decoders (code 0 = value 0 adds nothing to a branch metric); a HARD decoder has no neutral code for a
+ * punctured value and gets VD_ERR_OPTIONS.  An invalid pattern, or inputNum / 2 above 2^32 - 4097: VD_ERR_ARG.
+ * FP32 decoders want a scale like the harness's 40000 (values saturating the metric's [-8, 7]): at scale 1 the
+ * truncating FP32 branch metric loses a lone +-1 beside a punctured value. */
+
+/* floats in the received buffer for inputNum mother-code values: the kept positions among the first
+ * 2 * (inputNum / 2); 0 on an invalid pattern */
+size_t vd_punctured_len(int period, uint32_t keep0, uint32_t keep1, size_t inputNum);
+/* Fused depuncture + quantise + decode of device floats, under the rules of vd_run_device_llr (asynchronous, no
+ * allocation, capturable, the stream on the decoder's device).  rx_d needs 4-byte alignment only (single-dword
+ * loads; the 16-byte rule of the other float entry points does not apply). */
+int vd_run_device_punct(vd_decoder* dec, const float* rx_d, void* output_d, size_t inputNum, float scale,
+                        int period, uint32_t keep0, uint32_t keep1, void* stream);
+/* nbatch independent punctured batches in one launch: batch b reads rx_d + b * rx_stride bytes and writes
+ * output_d + b * output_stride bytes (both strides multiples of 4 bytes; rx_stride free as input_stride,
+ * output_stride as vd_run_device_batch). */
+int vd_run_device_punct_batch(vd_decoder* dec, const float* rx_d, size_t rx_stride, void* output_d,
+                              size_t output_stride, size_t inputNum, float scale, int period, uint32_t keep0,
+                              uint32_t keep1, int nbatch, void* stream);
+/* Blocking host-to-host variant (H2D of the vd_punctured_len floats, decode, D2H); kernel_ms as in vd_run. */
+int vd_run_punct(vd_decoder* dec, const float* rx_h, void* output_h, size_t inputNum, float scale, int period,
+                 uint32_t keep0, uint32_t keep1, float* kernel_ms);
+
 /* ---- the reference harness's channel source (RandBitGen | ConvolutionalEncoder | AddNoise |
  *      SoftDecisionPacker, viterbiDF.h:20-167), host and GPU ---- */
 
@@ -177,9 +210,10 @@ int vd_device_count(void);
 /* the kernels an option combination can run, for profilers (static strings) */
 const char* vd_kernel_name(int options);
 /* the kernel and launch form this decoder takes for a decode of inputNum encoded values in nbatch batches
- * (vd_run_device: nbatch 1; vd_run_device_batch: nbatch) of packed (llr 0) or float (llr 1) input, under
- * the knobs read at vd_create (VD_NO_PK, VD_PK_SPLIT, VD_NO_SPLIT); "-" when such a decode launches
- * nothing (fewer than one output word); valid until the thread's next call */
+ * (vd_run_device: nbatch 1; vd_run_device_batch: nbatch) of packed (llr 0), float (llr 1) or punctured
+ * float (llr 2: vd_decode_tg<PUN+...>) input, under the knobs read at vd_create (VD_NO_PK, VD_PK_SPLIT,
+ * VD_NO_SPLIT); "-" when such a decode launches nothing (fewer than one output word; llr 2 on a HARD
+ * decoder); valid until the thread's next call */
 const char* vd_decoder_kernel_name(vd_decoder* dec, size_t inputNum, int nbatch, int llr);
 /* build record: "<16 hex digits of the SHA-256 of the concatenated sources> <their paths, relative to the
  * package directory>"; the Python binding refuses a library whose sources have changed since (stale build) */
