@@ -170,11 +170,13 @@ def test_punctured_segment_launch(gpu, vd, vo, opt, pattern):
     rx = vd.puncture(channel_values_fast(n, 1.2, 13), pattern)
     dep = vd.depuncture(rx, pattern, n)
     ref = oracle_words(vo, opt, dep, nthreads=16)
-    caps = vd.split_cap_exits()
+    caps, before = vd.split_cap_exits(), vd.split_redecodes()
     with vd.ViterbiCUDA(opt) as d:
         kn = d.kernel_for(n, 1, 2)
         assert "vd_decode_tg<PUN+" in kn and "segment launch" in kn, kn
         out, _ = d.run_punct(rx, pattern, n, scale=SCALE)
+    # (codewords at snr 1.2: few re-decodes or none; tests/test_gpu_seg_count.py pins the count on noise)
+    print(f"{kn}: {vd.split_redecodes() - before} segments re-decoded")
     assert not differing(out, ref)
     assert vd.split_cap_exits() == caps == 0
 
