@@ -260,6 +260,11 @@ const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, i
     static thread_local std::string name;
     if (!d || nbatch < 1) return "-";
     if (llr == 2 && ch_of(d->options) == HARD) return "-";  // no punctured HARD kernels
+    if (llr == 3) {  // a frame launch: inputNum = maxFrameBits, nbatch = nframes
+        if (inputNum < 1 || inputNum > kFrmMaxBits) return "-";
+        name = plan_name(plan_frames(d->options, (uint64_t)nbatch), d->options, 3);
+        return name.c_str();
+    }
     name = plan_name(plan_of(d, inputNum, (uint32_t)nbatch, llr != 0, llr == 2), d->options, llr == 2 ? 2 : llr != 0);
     return name.c_str();
 }
@@ -540,6 +545,104 @@ int vd_run_punct(vd_decoder* d, const float* rx_h, void* output_h, size_t inputN
     if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
     if (rc != VD_OK) return rc;
     return run_staged(d, d->llr_d, rx_h, inB, output_h, outB, inputNum, true, scale, kernel_ms, &pn);
+}
+
+// ---- independent frames (vd_frames.h; vd_decode_tg<FRM+...>, one frame per wave) ----
+size_t vd_frame_output_size(int options, size_t frameBits)
+{
+    (void)options;  // whole 32-bit words for O_B32 and O_B16 (two 16-bit words each) alike
+    return 4 * ((frameBits + 31) / 32);
+}
+
+// the argument checks of a frame decode: VD_ERR_ARG / VD_ERR_OPTIONS
+static int frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, const void* output, size_t output_stride,
+                       size_t maxFrameBits, int nframes, int terminated, float scale, bool device)
+{
+    if (!d || !llr || !output) return fail(VD_ERR_ARG, "null argument");
+    if (const char* why = frame_args_error(device ? (uint64_t)(uintptr_t)llr : 0, llr_stride, output_stride, maxFrameBits,
+                                           nframes, scale))
+        return fail(VD_ERR_ARG, why);
+    if (ch_of(d->options) == HARD && !terminated)
+        return fail(VD_ERR_OPTIONS, "open frames on a HARD decoder: the stages after an open frame are erasures, and HARD's "
+                                    "v > 0 ? 1 : 0 has no neutral code; terminate the frames or use SOFT4, SOFT8, SOFT16 or FP32");
+    return VD_OK;
+}
+
+// the checks, then the one launch
+static int launch_frames(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
+                         const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
+                         hipStream_t s)
+{
+    int rc = frames_args(d, llr_d, llr_stride, output_d, output_stride, maxFrameBits, nframes, terminated, scale, true);
+    if (rc != VD_OK) return rc;
+    const int options = d->options;
+    const LaunchPlan p = plan_frames(options, (uint64_t)nframes);
+    launch_fn f = launcher_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1);
+    if (!f || !p.launches) return fail(VD_ERR_OPTIONS, "invalid options");
+    int sdev = -1;
+    if (s) VD_HIP(hipStreamGetDevice(s, &sdev));
+    else VD_HIP(hipGetDevice(&sdev));
+    if (sdev != d->device)
+        return fail(VD_ERR_ARG, "stream on device " + std::to_string(sdev) + ", decoder on device " +
+                                    std::to_string(d->device));
+    vd::Geom g;
+    g.packNum = 0;
+    g.availStages = 0;
+    g.nchunks = 1;
+    g.scale = scale;
+    g.fair = d->ds->board;
+    g.check = d->check;
+    g.nbatch = (uint32_t)nframes;
+    g.inStride = llr_stride;
+    g.outStride = output_stride;
+    g.frmBits = frame_bits_d;
+    g.frmMax = (uint32_t)maxFrameBits;
+    g.frmTerm = terminated ? 1u : 0u;
+    frame_pad(scale, &g.frmPad);  // (checked above)
+    f(llr_d, output_d, g, p.grid, s);
+    VD_HIP(hipGetLastError());
+    return VD_OK;
+}
+
+int vd_run_device_frames(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
+                         const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
+                         void* stream)
+{
+    return launch_frames(d, llr_d, llr_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes, terminated, scale,
+                         (hipStream_t)stream);
+}
+
+// the host buffers laid out like the device ones: nframes frames at llr_stride / output_stride bytes (the last
+// frame's part ends with its maxFrameBits stages / words); the staging buffers are the decoder's, the lengths
+// ride behind the floats
+int vd_run_frames(vd_decoder* d, const float* llr_h, size_t llr_stride, void* output_h, size_t output_stride,
+                  const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int terminated, float scale,
+                  float* kernel_ms)
+{
+    int rc = frames_args(d, llr_h, llr_stride, output_h, output_stride, maxFrameBits, nframes, terminated, scale, false);
+    if (rc != VD_OK) return rc;
+    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
+    const size_t inB = (size_t)(nframes - 1) * llr_stride + 8 * maxFrameBits;
+    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
+    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
+    VD_HIP(hipSetDevice(d->device));
+    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB);
+    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
+    if (rc != VD_OK) return rc;
+    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
+    VD_HIP(hipMemcpyAsync(d->llr_d, llr_h, inB, hipMemcpyHostToDevice, d->stream));
+    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
+    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
+    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
+    VD_HIP(hipEventRecord(d->ev0, d->stream));
+    rc = launch_frames(d, (const float*)d->llr_d, llr_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes, terminated,
+                       scale, d->stream);
+    if (rc != VD_OK) return rc;
+    VD_HIP(hipEventRecord(d->ev1, d->stream));
+    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
+    VD_HIP(hipStreamSynchronize(d->stream));
+    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    return VD_OK;
 }
 
 void* vd_host_alloc(size_t bytes)

@@ -43,6 +43,9 @@ constexpr int kLlr = 8;
 // 16 + base = float channel values of a punctured stream (SOFT4 .. FP32): the kept values only, found through
 // the pattern's index map in the loads that feed the table build and quantised like kLlr + base (TgInPun)
 constexpr int kPun = 16;
+// 24 + base = float channel values of independent frames, one frame per wave, decoded from first bit to last:
+// noise-free stages around the frame exist as a select in the loads (TgInFrm; vd_frames.h)
+constexpr int kFrm = 24;
 
 template <int CH>
 struct TgFmt {
@@ -653,6 +656,37 @@ __device__ __forceinline__ float2 tg_pun_load(__amdgpu_buffer_rsrc_t rs, const P
     return make_float2(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
 }
 
+// ---------------------------------------------------------------- frames (vd_frames.h)
+// A frame launch is a batched one-chunk launch: wave blockIdx.x * kWaves + wv decodes frame f (Geom::nbatch
+// frames) of S_f = min(frmBits[f], frmMax) stages into W_f = ceil(S_f / 32) words, as the one-chunk decode of
+// the frame's padded stream: 26 pad stages, the frame, then pad stages (terminated) or erasures (open).  The
+// padded stream is never stored.  One resource per frame, based at its first float with a range of 8 S_f
+// bytes; stage p of the padded stream is read at frame_offset(p) = 8 (p - 26), so every virtual stage falls
+// outside the range and loads zero -- for an open frame's suffix that already is the erasure.  The pad
+// replaces the loaded pair in the lanes of a pad stage where the values are used, at the table build one
+// group after the load, with the predicate recomputed from that group's first stage under a wave-uniform
+// branch that only groups touching a pad stage take (the first, and for terminated frames the ones from the
+// frame's end on): no flag waits in a VGPR for a group, and the prefetch is not waited on early.
+// Everything after the loads is TgInLlr<BASE>: the same quantisation, table rows, cores, ring and traceback.
+template <int BASE>
+struct TgInFrm : TgInLlr<BASE> {
+    static constexpr bool FRM = true;
+};
+template <> struct TgIn<kFrm + HARD> : TgInFrm<HARD> {};
+template <> struct TgIn<kFrm + SOFT4> : TgInFrm<SOFT4> {};
+template <> struct TgIn<kFrm + SOFT8> : TgInFrm<SOFT8> {};
+template <> struct TgIn<kFrm + SOFT16> : TgInFrm<SOFT16> {};
+template <> struct TgIn<kFrm + FP32> : TgInFrm<FP32> {};
+template <class T, class = void>
+struct HasFrm : std::false_type {};
+template <class T>
+struct HasFrm<T, std::void_t<decltype(T::FRM)>> : std::bool_constant<T::FRM> {};
+// the two values of stage p of the padded stream of the frame whose resource is rs (zero for a virtual stage)
+__device__ __forceinline__ float2 tg_frm_load(__amdgpu_buffer_rsrc_t rs, uint32_t p)
+{
+    return TgIn<FP32>::template load<0>(rs, frame_offset(p));
+}
+
 // ---------------------------------------------------------------- segment launches
 // A launch of 6400 chunks on 1024 SIMDs, one chunk per wave, puts 7 waves on a quarter of the SIMDs and
 // 6 on the rest, and the 7-wave SIMDs set the kernel time.  In a segment launch (Geom::seg) workgroup g
@@ -765,11 +799,23 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     const bool split = geo.seg != nullptr;
     const int piece = split ? wv : -1;
     const uint32_t gchunk = blockIdx.x * kWaves + wv;
-    const uint32_t batch = geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
+    constexpr bool FRM = HasFrm<IN>::value;  // frame launch: this wave decodes frame gchunk whole (never split)
+    uint32_t frmS = 0;                       // its stages (wave-uniform)
+    if constexpr (FRM) {
+        if (gchunk >= geo.nbatch) return;  // the last workgroup's waves past the last frame
+        const uint32_t n = geo.frmBits ? geo.frmBits[gchunk] : geo.frmMax;
+        frmS = __builtin_amdgcn_readfirstlane(n < geo.frmMax ? n : geo.frmMax);
+    }
+    const uint32_t batch = FRM ? gchunk : geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
     const void* const in = (const char*)in_all + batch * geo.inStride;
     void* const out = (char*)out_all + batch * geo.outStride;
+    // a chunk's first output word and its words (a frame: the chunk of its own one-chunk decode)
+    auto crange = [&](uint32_t c) {
+        if constexpr (FRM) return ChunkRange{0, frame_words(frmS) * (OB == 32 ? 1u : 2u)};
+        else return chunk_range(geo, c);
+    };
     auto words32 = [&](uint32_t c) {  // 32-bit words traced back in chunk c
-        const uint32_t w = chunk_range(geo, c).words;
+        const uint32_t w = crange(c).words;
         return OB == 32 ? w : (w + 1) / 2;
     };
     SegWG sw;
@@ -829,7 +875,8 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     // In a batched launch only the last batch's waves run the controller: earlier batches' waves are
     // followed by more work on their SIMD, so evening out progress buys nothing there and costs issue
     // (1.6 % per batch, profiles/r02/benchab_fair2.log).
-    fair.begin(batch + 1 < geo.nbatch ? nullptr : geo.fair, lane);
+    // (a frame launch: the waves of its last kChunks frames, as the last batch of a batched launch)
+    fair.begin((FRM ? batch + kChunks < geo.nbatch : batch + 1 < geo.nbatch) ? nullptr : geo.fair, lane);
     // fairness progress: blocks started, or in a segment launch the fraction of the segment's pass-0
     // blocks started, scaled to 2^20 (its waves differ in length)
     uint32_t fscale = 1u;
@@ -859,7 +906,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     const RunGeo rg = seg_run(sw, b0, b1, run);
     const uint32_t s0 = rg.s0, Sw = rg.words, E = rg.E;
     const int Xspec = rg.Xspec, Xcmp = rg.Xcmp;
-    const ChunkRange cr = chunk_range(geo, sw.c0 + (uint32_t)rg.i);
+    const ChunkRange cr = crange(sw.c0 + (uint32_t)rg.i);
     // local word k = chunk word s0 + k (32-bit words; O_B16 writes each as two 16-bit words)
     const uint64_t wOut = cr.startWord + s0;  // O_B32: output word of local word 0
     const uint64_t start = (uint64_t)cr.startWord * OB + 32ull * s0;  // first stage of the run
@@ -877,6 +924,10 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
         rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
         rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
+    } else if constexpr (FRM) {  // one resource for the whole frame: its 8 frmS bytes (start = 0, j0 = 0)
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(8u * frmS), 0x00020000);
+        rA = tg_frm_load(rs, (uint32_t)sA);
+        rB = tg_frm_load(rs, (uint32_t)sB);
     } else {
         rs = tg_rsrc<CH>(in, start + 32ull * j0, availB);
         rA = IN::template load<0>(rs, vo1);
@@ -1034,6 +1085,16 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     for (uint32_t j = j0;; j += 3) {
         // group head: the table from the inputs loaded one group ago, the next group's loads, then the
         // fairness board (its load returns during this group; nothing here waits on it)
+        if constexpr (FRM) {
+            // the pad value in the lanes of this group's pad stages (vd_frames.h): a uniform branch that the
+            // groups inside the frame skip
+            const uint32_t g0 = 32u * j, end = frame_end(frmS, geo.frmTerm != 0);
+            if (frame_pad_group(g0, end)) {
+                const float2 pad = make_float2(geo.frmPad, geo.frmPad);
+                if (frame_pad_stage(g0 + (uint32_t)sA, end)) rA = pad;
+                if (frame_pad_stage(g0 + (uint32_t)sB, end)) rB = pad;
+            }
+        }
         if constexpr (S01) {
             float s0, s1;
             IN::s01(rA, s0, s1);
@@ -1061,6 +1122,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             rs = tg_rsrc_pun(in, start + 32ull * (j + 3), availB, geo.pun, &r0);
             rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
             rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
+        } else if constexpr (FRM) {  // the next group's stages of the padded stream
+            rA = tg_frm_load(rs, 32u * (j + 3) + (uint32_t)sA);
+            rB = tg_frm_load(rs, 32u * (j + 3) + (uint32_t)sB);
         } else
         {  // the next group's input words
             rs = tg_rsrc<CH>(in, start + 32ull * (j + 3), availB);

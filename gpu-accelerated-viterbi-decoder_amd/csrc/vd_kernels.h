@@ -31,6 +31,7 @@
 #include <stdint.h>
 #include <utility>
 #include "vd_punct.h"
+#include "vd_frames.h"
 
 namespace vd {
 
@@ -67,6 +68,13 @@ struct Geom {
     // none) and the bytes of received values in each batch's buffer
     Punct pun;
     uint64_t punBytes = 0;
+    // frame launches (channel ids kFrm + format, vd_kernel_tg.h; vd_frames.h): nbatch frames, frame f at
+    // in + f * inStride -> out + f * outStride, of min(frmBits[f], frmMax) stages (frmBits null: frmMax each);
+    // frmTerm: the stages after a frame are pad stages (terminated) instead of erasures; frmPad: the pad value
+    const uint32_t* frmBits = nullptr;
+    uint32_t frmMax = 0;
+    uint32_t frmTerm = 0;
+    float frmPad = 0.0f;
 };
 // Progress board of the fairness controller: per SIMD slot (XCC, SE, SH, CU, SIMD from the hardware
 // wave id) kFairWaves 32-bit words, one per hardware wave slot of that SIMD (HW_ID.WAVE_ID): the blocks

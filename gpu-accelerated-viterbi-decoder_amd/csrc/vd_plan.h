@@ -2,12 +2,13 @@
 // the sizes, the knobs read at vd_create and the device's SIMD and segment-table counts (no HIP runtime calls,
 // no decoder: tests/cxx/plan_check.cpp checks it on the CPU), with the option helpers, the list of kernels
 // and the kernel names.  Shared by the C-ABI (vd_capi.hip) and the timing tools.
-// Include after vd_kernel_tg.h (kSplitMinWords, kLlr, kPun; the tools include their ablation copy of it).
+// Include after vd_kernel_tg.h (kSplitMinWords, kLlr, kPun, kFrm; the tools include their ablation copy of it).
 #pragma once
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include "vd_frames.h"
 #include "vd_segplan.h"
 
 namespace vd {
@@ -139,6 +140,26 @@ typename L::fn launcher_punct(int ch, int me, bool o16)
     return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
 }
 
+// Frame launches (channel ids kFrm + format, vd_kernel_tg.h; vd_frames.h): vd_decode_tg only, all 12 pairs x
+// {O32, O16} (HARD too: a terminated frame needs no neutral code), again in a table of their own.
+template <class L>
+typename L::fn launcher_frames(int ch, int me, bool o16)
+{
+    struct Table {
+        typename L::fn at[5][3][2] = {};
+        Table()
+        {
+#define VD_X(C, M)                                      \
+    at[C][M][0] = &L::template tg<kFrm + C, M, 32>;     \
+    at[C][M][1] = &L::template tg<kFrm + C, M, 16>;
+            VD_TG_PAIRS(VD_X)
+#undef VD_X
+        }
+    };
+    static const Table t;
+    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
+}
+
 // ---------------------------------------------------------------- the knobs (read once, at vd_create)
 struct Knobs {
     int split = 1;    // segment launches: 0 none (VD_NO_SPLIT=1), 1 pieces, 2 thirds, 3 sevenths (VD_SPLIT=...)
@@ -220,17 +241,30 @@ inline LaunchPlan plan_launch(int o, size_t inputNum, uint32_t nbatch, bool llr,
     return p;
 }
 
+// nframes independent frames (vd_frames.h): one frame per wave on vd_decode_tg<FRM+...>, whatever the knobs say
+// (no vd_decode_pk twins, no segment launch: a frame is never split)
+inline LaunchPlan plan_frames(int o, uint64_t nframes)
+{
+    LaunchPlan p;
+    p.launches = valid(o) && nframes != 0;
+    p.form = Form::Tg;
+    p.grid = (unsigned)((nframes + kWaves - 1) / kWaves);
+    return p;
+}
+
 // ---------------------------------------------------------------- names
 inline constexpr const char* kChNames[5] = {"HARD", "SOFT4", "SOFT8", "SOFT16", "FP32"};
 inline constexpr const char* kCoreNames[3] = {"B32", "B16", "F16"};
 
 // vd_decoder_kernel_name: the kernel and launch form of one planned launch; input: 0 packed words, 1 float
-// channel values (LLR), 2 punctured float values (PUN)
+// channel values (LLR), 2 punctured float values (PUN), 3 frames of float values (FRM; a plan of plan_frames)
 inline std::string plan_name(const LaunchPlan& p, int o, int input)
 {
     if (!p.launches) return "-";
-    const std::string args = std::string(input == 2 ? "PUN+" : input ? "LLR+" : "") + kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," +
+    const std::string args = std::string(input == 3 ? "FRM+" : input == 2 ? "PUN+" : input ? "LLR+" : "") + kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," +
                              (out_of(o) ? "O16" : "O32") + ">";
+    if (input == 3)
+        return "vd_decode_tg<" + args + " one frame per wave, " + (ch_of(o) == SOFT16 ? "int32 tagged patterns" : "fp32 tagged core");
     if (p.form == Form::PkBatched) return "vd_decode_pk<" + args + " batched: two chunks per wave, int16 halves";
     if (p.form == Form::PkSplit) return "vd_decode_pk<" + args + " split: one chunk per wave cut in two, int16 halves";
     return "vd_decode_tg<" + args + (p.seg != kSegNone ? " segment launch: one chunk or piece per wave, " : " one chunk per wave, ") +

@@ -47,7 +47,7 @@ EXPORTS = ["vd_options_valid", "vd_input_size", "vd_message_len", "vd_output_siz
            "vd_run_stream", "vd_channel_device", "vd_simulate_device", "vd_mt_state_after", "vd_split_redecodes",
            "vd_split_cap_exits", "vd_set_guard_check", "vd_guard_violations", "vd_run_device_llr_batch", "vd_build_info",
            "vd_decoder_kernel_name", "vd_punctured_len", "vd_run_device_punct", "vd_run_device_punct_batch",
-           "vd_run_punct"]
+           "vd_run_punct", "vd_frame_output_size", "vd_run_device_frames", "vd_run_frames"]
 
 # puncture patterns (period, keep0, keep1): bit i of keep0 / keep1 = the first (0171) / second (0133) encoder
 # output of the stages t with t % period == i is transmitted.  Any valid masks decode (and equal the rate-1/2
@@ -105,6 +105,9 @@ def lib():
            "vd_run_device_punct": ([vp, vp, vp, sz, f, i, ctypes.c_uint32, ctypes.c_uint32, vp], None),
            "vd_run_device_punct_batch": ([vp, vp, sz, vp, sz, sz, f, i, ctypes.c_uint32, ctypes.c_uint32, i, vp], None),
            "vd_run_punct": ([vp, vp, vp, sz, f, i, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(f)], None),
+           "vd_frame_output_size": ([i, sz], sz),
+           "vd_run_device_frames": ([vp, vp, sz, vp, sz, vp, sz, i, i, f, vp], None),
+           "vd_run_frames": ([vp, vp, sz, vp, sz, vp, sz, i, i, f, ctypes.POINTER(f)], None),
            "vd_kernel_name": ([i], ctypes.c_char_p),
            "vd_decoder_kernel_name": ([vp, sz, i, i], ctypes.c_char_p)}
     for name, (args, res) in sig.items():
@@ -252,7 +255,8 @@ class ViterbiCUDA:
     def kernel_for(self, inputNum, nbatch=1, llr=False):
         """the kernel and launch form this decoder runs for nbatch batches of inputNum values
         (vd_decoder_kernel_name: follows VD_NO_PK / VD_PK_SPLIT / VD_NO_SPLIT as read at creation); llr: False /
-        0 packed input, True / 1 float channel values, 2 punctured float values"""
+        0 packed input, True / 1 float channel values, 2 punctured float values, 3 a frame launch (inputNum =
+        maxFrameBits, nbatch = nframes)"""
         return lib().vd_decoder_kernel_name(self._h, inputNum, nbatch, int(llr)).decode()
 
     def set_guard_check(self, enable=True):
@@ -340,6 +344,42 @@ class ViterbiCUDA:
         _check(lib().vd_run_device_punct_batch(self._h, ctypes.c_void_p(rx_ptr), rx_stride, ctypes.c_void_p(output_ptr),
                                                output_stride, inputNum, scale, *pattern, nbatch, ctypes.c_void_p(stream)))
 
+    # ---- independent frames, decoded from first bit to last (vd_capi.h "independent frames") ----
+    def run_frames(self, llr_h, terminated=True, scale=40000.0, frame_bits=None):
+        """Blocking decode of nframes frames in one launch.  llr_h: float array [nframes, 2 * maxFrameBits], frame f
+        in row f (first encoder output first, encoder started in state 0); frame_bits: the stages of each frame
+        (values above maxFrameBits count as maxFrameBits, 0 decodes nothing), default maxFrameBits each;
+        terminated: the frames end with six tail zeros (else open frames: not on HARD decoders).  Frame f
+        equals, word for word, the one-chunk decode of pad_frame(its values, ...).  Returns (out, ms): out
+        [nframes, words] of decPack_t, 4 * ceil(maxFrameBits / 32) bytes a row, bit i of a row (MSB first)
+        information bit i of the frame; the words past a shorter frame's own stay 0."""
+        llr_h = np.ascontiguousarray(llr_h, dtype=np.float32)
+        if llr_h.ndim != 2 or llr_h.shape[1] % 2:
+            raise VitdecError("run_frames: llr_h must be [nframes, 2 * maxFrameBits]")
+        nframes, max_bits = llr_h.shape[0], llr_h.shape[1] // 2
+        row = frame_output_size(self.options, max_bits)
+        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
+        fb = None
+        if frame_bits is not None:
+            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
+            if fb.shape != (nframes,):
+                raise VitdecError("run_frames: frame_bits must hold one length per frame")
+        ms = ctypes.c_float(0.0)
+        _check(lib().vd_run_frames(self._h, llr_h.ctypes.data, 8 * max_bits, out.ctypes.data, row,
+                                   fb.ctypes.data if fb is not None else None, max_bits, nframes, 1 if terminated else 0,
+                                   scale, ctypes.byref(ms)))
+        return out, ms.value
+
+    def run_device_frames(self, llr_ptr, llr_stride, output_ptr, output_stride, maxFrameBits, nframes, terminated=True,
+                          scale=40000.0, frame_bits_ptr=0, stream=0):
+        """Async decode of nframes frames in one launch (vd_run_device_frames): frame f reads its 2 S_f floats at
+        llr_ptr + f * llr_stride bytes (8-byte aligned) and writes 4 * ceil(S_f / 32) bytes at output_ptr + f *
+        output_stride; S_f = min(lengths[f], maxFrameBits) with frame_bits_ptr a device array of uint32 lengths,
+        or maxFrameBits when it is 0."""
+        _check(lib().vd_run_device_frames(self._h, ctypes.c_void_p(llr_ptr), llr_stride, ctypes.c_void_p(output_ptr),
+                                          output_stride, ctypes.c_void_p(frame_bits_ptr) if frame_bits_ptr else None,
+                                          maxFrameBits, nframes, 1 if terminated else 0, scale, ctypes.c_void_p(stream)))
+
 
 class PinnedArray:
     """A numpy view of page-locked host memory from vd_host_alloc (freed with the object)."""
@@ -389,6 +429,45 @@ def depuncture(rx, pattern, inputNum):
     kept = _kept(pattern, inputNum)
     out = np.zeros(inputNum, dtype=np.float32)
     out[:kept.size][kept] = np.asarray(rx, dtype=np.float32).reshape(-1)[:int(kept.sum())]
+    return out
+
+
+def frame_output_size(options, frameBits):
+    """bytes a frame of frameBits stages decodes to: 4 * ceil(frameBits / 32) (vd_frame_output_size)"""
+    return lib().vd_frame_output_size(options, frameBits)
+
+
+FRAME_LEAD = 26  # pad stages before a frame: the reference's extraL, where a decode window starts emitting bits
+
+
+def pad_frame(values, terminated, scale, opt):
+    """The padded stream that defines a frame decode (host helper; the contract the tests feed to the oracle).
+
+    values: the 2 S floats of a frame of S stages.  Returns the 2 P floats, P = 64 + 32 ceil(S / 32), of
+    26 pad stages, the frame, and pad stages (terminated) or +0.0 erasures (open frame) up to P; the frame
+    decode equals the one-chunk decode (nchunks = 1, inputNum = 2 P) of its SoftDecisionPacker(opt, scale)
+    packing, and decoded bit i is information bit i of the frame.  The pad float is -32768 / scale rounded
+    away from zero, so that it quantises to the most negative code of every format (HARD bit 0, SOFT4 -8,
+    SOFT8 -128, SOFT16 -32768, FP32 -8 after the clamp): the same code as the decode kernel's own pad value
+    (-65536 / scale), hence the same branch metrics.  Open frames need a neutral code: not with HARD."""
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    if v.size % 2:
+        raise VitdecError("pad_frame: two values per stage")
+    if not terminated and (opt & CHANNEL_MASK) == HARD:
+        raise VitdecError("pad_frame: an open frame needs a neutral code, HARD has none")
+    sc = np.float32(scale)
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(sc) and sc > 0 and np.isfinite(np.float32(-65536.0) / sc)
+    if not ok:  # (the entry points' rule, VD_ERR_ARG there)
+        raise VitdecError("pad_frame: scale must be finite and > 0 (and -65536 / scale finite)")
+    pad = np.float32(-32768.0) / sc
+    if pad * sc > np.float32(-32768.0):
+        pad = np.nextafter(pad, np.float32(-np.inf))
+    S = v.size // 2
+    P = 64 + 32 * ((S + 31) // 32)
+    out = np.full(2 * P, pad if terminated else 0.0, dtype=np.float32)
+    out[:2 * FRAME_LEAD] = pad
+    out[2 * FRAME_LEAD:2 * (FRAME_LEAD + S)] = v
     return out
 
 

@@ -163,6 +163,42 @@ int vd_run_device_punct_batch(vd_decoder* dec, const float* rx_d, size_t rx_stri
 int vd_run_punct(vd_decoder* dec, const float* rx_h, void* output_h, size_t inputNum, float scale, int period,
                  uint32_t keep0, uint32_t keep1, float* kernel_ms);
 
+/* ---- independent frames, decoded from first bit to last (new; the reference decodes one long stream and
+ *      never its first 26 and last 38 bits) ----
+ * A frame is S trellis stages: 2 S float channel values, first encoder output first, of an encoder started in
+ * state 0 and either flushed back to state 0 by six tail zeros (terminated = 1: the frame's last six
+ * information bits are zeros) or simply stopped (terminated = 0, an open frame).  With W = ceil(S / 32) and
+ * P = 64 + 32 W, the frame decode equals, word for word, the one-chunk decode (inputNum = 2 P) of the frame's
+ * padded stream: stages [0, 26) hold the pad value twice, stages [26, 26 + S) the frame, and the stages from
+ * 26 + S on the pad value (terminated) or +0.0f, an erasure (open).  The pad value is the one whose
+ * quantisation is the format's most negative code, "both encoder outputs 0" at full confidence (HARD bit 0,
+ * SOFT4 -8, SOFT8 -128, SOFT16 -32768, FP32 -8 after the clamp), whatever the scale.  It writes W 32-bit words
+ * (O_B16: 2 W 16-bit words); decoded bit i (MSB first, as vd_count_errors reads it) is information bit i of the
+ * frame, and the bits of the last word past S decode the padding (0 for a terminated frame).  The padded stream
+ * is never stored: the virtual stages are a select in the loads of the branch-metric table build, one wave
+ * decodes one frame, and all frames go in one launch.  Every format and metric; an open frame needs a neutral
+ * code, so a HARD decoder with terminated = 0 gets VD_ERR_OPTIONS.  VD_ERR_ARG: maxFrameBits outside
+ * [1, 2^20], nframes < 1, scale not finite and > 0, a misaligned pointer or stride, overlapping frames.
+ * Punctured frames, packed-word frames, frames longer than 2^20 stages and tail-biting are not supported. */
+
+/* bytes a frame of frameBits stages decodes to: 4 * ceil(frameBits / 32), for O_B32 and O_B16 alike */
+size_t vd_frame_output_size(int options, size_t frameBits);
+/* nframes frames in one launch, under the rules of vd_run_device_llr (asynchronous, no allocation, capturable,
+ * the stream on the decoder's device).  Frame f reads 2 S_f floats at llr_d + f * llr_stride bytes and writes
+ * vd_frame_output_size(S_f) bytes at output_d + f * output_stride bytes, S_f = min(frame_bits_d[f],
+ * maxFrameBits), or maxFrameBits when frame_bits_d is NULL; a frame of 0 stages writes nothing, and no byte
+ * outside a frame's words is written.  Nothing outside a frame's 2 S_f floats is read.  llr_d 8-byte aligned,
+ * llr_stride a multiple of 8, output_stride a multiple of 4; with nframes > 1, llr_stride >= 8 * maxFrameBits
+ * and output_stride >= vd_frame_output_size(maxFrameBits). */
+int vd_run_device_frames(vd_decoder* dec, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
+                         const uint32_t* frame_bits_d /* device, or NULL: every frame has maxFrameBits */,
+                         size_t maxFrameBits, int nframes, int terminated, float scale, void* stream);
+/* Blocking host-to-host variant over host buffers of the same layout (H2D, the launch, D2H); the output bytes
+ * no frame writes keep their values.  kernel_ms as in vd_run. */
+int vd_run_frames(vd_decoder* dec, const float* llr_h, size_t llr_stride, void* output_h, size_t output_stride,
+                  const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int terminated, float scale,
+                  float* kernel_ms);
+
 /* ---- the reference harness's channel source (RandBitGen | ConvolutionalEncoder | AddNoise |
  *      SoftDecisionPacker, viterbiDF.h:20-167), host and GPU ---- */
 
@@ -213,7 +249,8 @@ const char* vd_kernel_name(int options);
  * (vd_run_device: nbatch 1; vd_run_device_batch: nbatch) of packed (llr 0), float (llr 1) or punctured
  * float (llr 2: vd_decode_tg<PUN+...>) input, under the knobs read at vd_create (VD_NO_PK, VD_PK_SPLIT,
  * VD_NO_SPLIT); "-" when such a decode launches nothing (fewer than one output word; llr 2 on a HARD
- * decoder); valid until the thread's next call */
+ * decoder); llr 3: the frame launch of vd_run_device_frames (vd_decode_tg<FRM+...>), with inputNum =
+ * maxFrameBits and nbatch = nframes; valid until the thread's next call */
 const char* vd_decoder_kernel_name(vd_decoder* dec, size_t inputNum, int nbatch, int llr);
 /* build record: "<16 hex digits of the SHA-256 of the concatenated sources> <their paths, relative to the
  * package directory>"; the Python binding refuses a library whose sources have changed since (stale build) */
