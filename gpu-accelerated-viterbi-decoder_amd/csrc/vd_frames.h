@@ -15,6 +15,7 @@
 // helpers below against a plain enumeration.
 #pragma once
 #include <stdint.h>
+#include "vd_punct.h"
 
 #if defined(__HIPCC__)
 #define VD_FRAMES_HD __host__ __device__ inline
@@ -78,6 +79,82 @@ inline const char* frame_args_error(uint64_t llr_addr, uint64_t llr_stride, uint
     if (llr_addr & 7) return "llr_d must be 8-byte aligned";
     if ((llr_stride & 7) || (output_stride & 3)) return "llr_stride % 8 or output_stride % 4 != 0";
     if (nframes > 1 && llr_stride < 8 * maxFrameBits) return "llr_stride smaller than 8 * maxFrameBits: frames would overlap";
+    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
+        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- punctured frames (channel ids kFrm + kPun + format)
+// A punctured frame of S stages under a pattern (vd_punct.h) holds the punct_len(2 S) kept values of its 2 S
+// mother-code values, the pattern's phase restarting at the frame's first stage: frame stage t uses bit
+// t % period.  Its decode is the frame decode above of the depunctured frame (+0.0f at the punctured positions).
+// One resource per frame, based at its first received float with a range of its received bytes.  A 96-stage group
+// from padded stage g0 starts at frame stage t0 = g0 - 26 (group 0: its lanes s < 26 are lead stages, lane s >= 26
+// is frame stage s - 26); (q0, r0) of t0 by punct_divmod on the scalar unit, and lane s reads its two values at
+// byte 4 (q0 Kp + punct_rel(r0, s - lead)), a vector offset.  The kept indices grow with the stage, so a stage
+// >= S lands at or past the range's end and loads zero by the range check alone; punctured values and lead stages
+// take kFrmOutside (every other offset stays below 2^24: no 32-bit wrap of offset + 4).
+// tests/cxx/punct_frames_check.cpp checks the helpers below against a plain enumeration.
+
+// the received bytes of a punctured frame of S <= kFrmMaxBits stages: 4 punct_len(2 S), at most 8 MiB
+VD_FRAMES_HD uint32_t pfrm_bytes(const Punct& pn, uint32_t S)
+{
+    uint32_t q, r;
+    punct_divmod(pn, S, q, r);
+    return 4u * (q * pn.kp + punct_before(pn, r));
+}
+// the group from padded stage g0 (a multiple of kFrmGroup): its first frame stage t0, and the lanes s < lead
+// that lie before the frame
+struct PfrmGroup {
+    uint32_t t0, lead;
+};
+VD_FRAMES_HD constexpr PfrmGroup pfrm_group(uint32_t g0)
+{
+    return g0 < kFrmLead ? PfrmGroup{0u, kFrmLead - g0} : PfrmGroup{g0 - kFrmLead, 0u};
+}
+// byte offset of float q0 Kp, (q0, r0) = divmod(t0, period); *r0 = t0 % period
+VD_FRAMES_HD uint32_t pfrm_base(const Punct& pn, uint32_t t0, uint32_t* r0)
+{
+    uint32_t q0;
+    punct_divmod(pn, t0, q0, *r0);
+    return q0 * (pn.kp * 4u);
+}
+// the byte offsets of the two values of lane s (< kFrmGroup) of the group (base4, r0, lead) against the frame's
+// resource: inside the range exactly for a kept value of a frame stage < S
+struct PfrmOff {
+    uint32_t o0, o1;
+};
+// a b for a, b < 2^24: the masks change nothing and let the compiler take the full-rate 24-bit multiply
+// (v_mul_u32_u24 / v_mad_u32_u24, which ignore the upper bits: the masks cost no instruction) where the 32-bit
+// v_mul_lo_u32 issues at a quarter of the rate -- six of those per group were most of this path's cost
+VD_FRAMES_HD uint32_t pfrm_mul24(uint32_t a, uint32_t b) { return (a & 0xFFFFFFu) * (b & 0xFFFFFFu); }
+VD_FRAMES_HD PfrmOff pfrm_offsets(const Punct& pn, uint32_t base4, uint32_t r0, uint32_t lead, uint32_t s)
+{
+    const uint32_t before = s < lead ? kFrmOutside : 0u;
+    // punct_rel's map of x = r0 + (s - lead) < 16 + kPunctSpan (its reciprocal proof holds unchanged), with
+    // 24-bit products: x m16 < 112 (2^16 + 1) < 2^23, dq < 112
+    const uint32_t x = r0 + (s < lead ? 0u : s - lead);
+    const uint32_t dq = pfrm_mul24(x, pn.m16) >> 16;
+    const uint32_t r = x - pfrm_mul24(dq, pn.period);
+    const uint32_t has0 = (pn.keep0 >> r) & 1u, has1 = (pn.keep1 >> r) & 1u;
+    const uint32_t b = base4 + pfrm_mul24(dq, 4u * pn.kp) + (punct_before(pn, r) << 2);
+    return {b | ((has0 ^ 1u) * kFrmOutside) | before, (b + (has0 << 2)) | ((has1 ^ 1u) * kFrmOutside) | before};
+}
+
+// The argument checks of vd_run_device_punct_frames (all VD_ERR_ARG): the message, or null when the arguments are
+// good.  rx_addr: the address of the first frame's first float; maxFrameBits counts stages.
+inline const char* pfrm_args_error(uint64_t rx_addr, uint64_t rx_stride, uint64_t output_stride, uint64_t maxFrameBits,
+                                   int nframes, float scale, int period, uint32_t keep0, uint32_t keep1)
+{
+    float pad;
+    if (!punct_valid(period, keep0, keep1))
+        return "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
+    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
+    if (nframes < 1) return "nframes must be >= 1";
+    if (!frame_pad(scale, &pad)) return "scale must be finite and > 0 (and -65536 / scale finite)";
+    if ((rx_addr | rx_stride | output_stride) & 3) return "rx_d, rx_stride and output_stride must be multiples of 4 bytes";
+    if (nframes > 1 && rx_stride < pfrm_bytes(punct_make(period, keep0, keep1), (uint32_t)maxFrameBits))
+        return "rx_stride smaller than 4 * vd_punctured_len(2 * maxFrameBits): frames would overlap";
     if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
         return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
     return nullptr;

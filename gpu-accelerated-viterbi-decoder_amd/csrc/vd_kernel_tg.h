@@ -46,6 +46,7 @@ constexpr int kPun = 16;
 // 24 + base = float channel values of independent frames, one frame per wave, decoded from first bit to last:
 // noise-free stages around the frame exist as a select in the loads (TgInFrm; vd_frames.h)
 constexpr int kFrm = 24;
+// kFrm + kPun + base = the kept float values of independent punctured frames, one frame per wave (TgInPfr)
 
 template <int CH>
 struct TgFmt {
@@ -687,6 +688,38 @@ __device__ __forceinline__ float2 tg_frm_load(__amdgpu_buffer_rsrc_t rs, uint32_
     return TgIn<FP32>::template load<0>(rs, frame_offset(p));
 }
 
+// ---------------------------------------------------------------- punctured frames (vd_frames.h "punctured frames")
+// kFrm + kPun + base = the kept float values of independent punctured frames (SOFT4 .. FP32), one frame per wave.
+// A frame launch in everything but the loads (FRM: the wave's frame and length, its output words, the fairness
+// rule, the pad select at the table build), and the loads compose TgInPun's index map with TgInFrm's padded
+// stream: one resource per frame over its received bytes (pfrm_bytes, once per wave on the scalar unit), per
+// group the scalar (4 q0 Kp, r0) of its first frame stage (pfrm_group, pfrm_base), per lane two single-dword
+// loads at the vector offsets of pfrm_offsets.  Punctured values, lead stages and every stage from the frame's
+// end on read zero through the range check: no flag waits in a VGPR.  The first loads of a wave are group 0's
+// (lead 26, frame stage 0: q0 = r0 = 0), every later group has no lead stage, so both forms fold at compile time.
+template <int BASE>
+struct TgInPfr : TgInLlr<BASE> {
+    static_assert(BASE != HARD, "HARD has no neutral code for an erasure");
+    static constexpr bool FRM = true;
+    static constexpr bool PFR = true;
+};
+template <> struct TgIn<kFrm + kPun + SOFT4> : TgInPfr<SOFT4> {};
+template <> struct TgIn<kFrm + kPun + SOFT8> : TgInPfr<SOFT8> {};
+template <> struct TgIn<kFrm + kPun + SOFT16> : TgInPfr<SOFT16> {};
+template <> struct TgIn<kFrm + kPun + FP32> : TgInPfr<FP32> {};
+template <class T, class = void>
+struct HasPfr : std::false_type {};
+template <class T>
+struct HasPfr<T, std::void_t<decltype(T::PFR)>> : std::bool_constant<T::PFR> {};
+// the two values of lane stage s (< 96) of the group from padded stage g0 of the frame whose resource is rs
+__device__ __forceinline__ float2 tg_pfr_load(__amdgpu_buffer_rsrc_t rs, const Punct& pn, uint32_t base4, uint32_t r0,
+                                              uint32_t lead, uint32_t s)
+{
+    const PfrmOff o = pfrm_offsets(pn, base4, r0, lead, s);
+    const uint32_t x = __builtin_amdgcn_raw_buffer_load_b32(rs, o.o0, 0, 0), y = __builtin_amdgcn_raw_buffer_load_b32(rs, o.o1, 0, 0);
+    return make_float2(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
+}
+
 // ---------------------------------------------------------------- segment launches
 // A launch of 6400 chunks on 1024 SIMDs, one chunk per wave, puts 7 waves on a quarter of the SIMDs and
 // 6 on the rest, and the 7-wave SIMDs set the kernel time.  In a segment launch (Geom::seg) workgroup g
@@ -796,7 +829,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     // This wave's work: chunk blockIdx.x * kWaves + wv, or, in a segment launch (Geom::seg), segment wv of
     // the workgroup's chunks -- see "segment launches" above.
     // A batched launch (Geom::nbatch > 1) decodes chunk c of batch b at launch chunk b * nchunks + c.
-    const bool split = geo.seg != nullptr;
+    // (a frame is never split: the punctured-frame kernels are compiled without the segment machinery, which
+    // otherwise costs the SOFT8 / M_B16 one a spilled VGPR)
+    const bool split = HasPfr<IN>::value ? false : geo.seg != nullptr;
     const int piece = split ? wv : -1;
     const uint32_t gchunk = blockIdx.x * kWaves + wv;
     constexpr bool FRM = HasFrm<IN>::value;  // frame launch: this wave decodes frame gchunk whole (never split)
@@ -806,6 +841,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         const uint32_t n = geo.frmBits ? geo.frmBits[gchunk] : geo.frmMax;
         frmS = __builtin_amdgcn_readfirstlane(n < geo.frmMax ? n : geo.frmMax);
     }
+    constexpr bool PFR = HasPfr<IN>::value;  // ... of the kept values of a punctured frame (tg_pfr_load)
+    uint32_t pfrB = 0;                       // its received bytes (wave-uniform)
+    if constexpr (PFR) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes(geo.pun, frmS));
     const uint32_t batch = FRM ? gchunk : geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
     const void* const in = (const char*)in_all + batch * geo.inStride;
     void* const out = (char*)out_all + batch * geo.outStride;
@@ -919,7 +957,13 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     uint32_t tbn = pass == 0 ? LL::TBS - 3 * (blockIdx.x & 3) : LL::TBS;
     __amdgpu_buffer_rsrc_t rs;
     typename IN::raw_t rA, rB;  // the input of stages sA and sB of the group
-    if constexpr (PUN) {
+    if constexpr (PFR) {  // one resource for the whole frame: its received bytes; group 0 (start = 0, j0 = 0)
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)pfrB, 0x00020000);
+        constexpr PfrmGroup pg = pfrm_group(0u);
+        static_assert(pg.t0 == 0, "group 0 starts at frame stage 0: q0 = r0 = 0");
+        rA = tg_pfr_load(rs, geo.pun, 0u, 0u, pg.lead, (uint32_t)sA);
+        rB = tg_pfr_load(rs, geo.pun, 0u, 0u, pg.lead, (uint32_t)sB);
+    } else if constexpr (PUN) {
         uint32_t r0;
         rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
         rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
@@ -1117,7 +1161,16 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
                 put_row(P1{}, A, B, r6b);
             }
         }
-        if constexpr (PUN) {  // the next group's received values, at the offsets of its own r0
+        if constexpr (PFR) {  // the next group's kept values: (4 q0 Kp, r0) of its first frame stage, scalar unit
+            const uint32_t g0n = 32u * (j + 3);
+            __builtin_assume(g0n >= kFrmGroup);  // (no lead stage: pg.lead folds to 0)
+            const PfrmGroup pg = pfrm_group(g0n);
+            uint32_t r0;
+            const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
+            r0 = __builtin_amdgcn_readfirstlane(r0);
+            rA = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sA);
+            rB = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sB);
+        } else if constexpr (PUN) {  // the next group's received values, at the offsets of its own r0
             uint32_t r0;
             rs = tg_rsrc_pun(in, start + 32ull * (j + 3), availB, geo.pun, &r0);
             rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
