@@ -160,4 +160,86 @@ inline const char* pfrm_args_error(uint64_t rx_addr, uint64_t rx_stride, uint64_
     return nullptr;
 }
 
+// ---------------------------------------------------------------- tail-biting frames (channel ids kFrm + kTb + format)
+// A tail-biting frame of S >= 1 stages: the encoder's register at the first stage holds the frame's last six
+// information bits (cyclically for S < 6), so output stage t depends on bits t, t - 1, ..., t - 6 mod S, start
+// state = end state, no tail.  Its decode is the one-chunk decode of the frame's extended stream of P = 64 + 32 W
+// stages, stage p = frame stage (p - 26) mod S (non-negative residue, as many turns as it takes; the same rule
+// for what the kernel prefetches beyond P): the interior of a periodic stream, which the fixed window decodes as
+// it decodes any interior chunk.  No pad, no erasure: every format, HARD included.
+// The frame's resource is the frame launch's (based at its first float, 8 S bytes), and every load offset lies
+// inside it: 8 t with t < S.  A 96-stage group from g0 reads frame stages g0 - 26 + s, s < 96, unwrapped (offset
+// 8 (p - 26), frame_offset without its clamp) unless it is group 0 (its lanes s < 26 lie before the frame) or
+// reaches the frame's end (g0 + 96 - 26 > S): tb_wrap_group, wave-uniform.  A wrapping group reduces its first
+// stage once on the scalar unit, r0 = (g0 - 26) mod S (tb_group_r0, with the wave's reciprocal of S from set-up),
+// and lane s reduces x = r0 + s < S + 96 (tb_lane_stage).  tests/cxx/tb_frames_check.cpp checks the helpers
+// below against a plain enumeration.
+
+// The wave's reciprocals of its S (1 <= S <= kFrmMaxBits; one division at set-up):
+//   m32 = floor((2^32 - 1) / S): (2^32 - 1) / S - 1 < m32 <= (2^32 - 1) / S, so for x < 2^31 the estimate
+//     qe = floor(x m32 / 2^32) has x / S - x m32 / 2^32 < x (1 / (S 2^32) + 1 / 2^32) <= 2 x / 2^32 < 1:
+//     qe is floor(x / S) or one below, and x - qe S lies in [0, 2 S): one conditional subtract (tb_mod);
+//   m16 = (m32 >> 16) + 1 (used for S < 96 only): m32 >> 16 = floor((2^32 - 1) / (2^16 S)) is floor(2^16 / S),
+//     or one below when S divides 2^16, so m16 S = 2^16 + e with 0 <= e <= S <= 95, and for x < 192:
+//     x m16 / 2^16 = x / S + x e / (S 2^16) with x e <= 191 * 95 < 2^16, less than the 1 / S that x / S lacks
+//     to the next integer at least: floor(x m16 / 2^16) = floor(x / S) exactly (punct_rel's argument).
+struct TbRecip {
+    uint32_t m32, m16;
+};
+VD_FRAMES_HD TbRecip tb_recip(uint32_t S)
+{
+    const uint32_t m32 = 0xFFFFFFFFu / S;
+    return {m32, (m32 >> 16) + 1u};
+}
+// x mod S for x < 2^31 (uniform operands: one scalar multiply-high, one multiply, a subtract and a minimum)
+VD_FRAMES_HD uint32_t tb_mod(uint32_t x, uint32_t S, uint32_t m32)
+{
+    const uint32_t r = x - (uint32_t)(((uint64_t)x * m32) >> 32) * S;  // in [0, 2 S)
+    return r - S < r ? r - S : r;                                      // (r - S wraps above r when r < S)
+}
+// some lane of the 96-stage group from extended stage g0 (a multiple of kFrmGroup) wraps: wave-uniform
+VD_FRAMES_HD bool tb_wrap_group(uint32_t g0, uint32_t S) { return g0 < kFrmLead || g0 + kFrmGroup - kFrmLead > S; }
+// frame stage of the group's lane 0: (g0 - 26) mod S, non-negative (g0 <= kFrmMaxBits + a few groups)
+VD_FRAMES_HD uint32_t tb_group_r0(uint32_t g0, uint32_t S, uint32_t m32)
+{
+    if (g0 >= kFrmLead) return tb_mod(g0 - kFrmLead, S, m32);
+    const uint32_t a = tb_mod(kFrmLead - g0, S, m32);
+    return a ? S - a : 0u;
+}
+// frame stage of lane s (< kFrmGroup) of a wrapping group: (r0 + s) mod S, r0 < S.  x = r0 + s < S + 96: for
+// S >= 96 that is below 2 S, one conditional subtract (as a minimum: no select); for S < 96, x < 192 and the
+// 16-bit reciprocal is exact (above), in 24-bit products: x < 192, m16 <= 65537, x m16 < 2^24, dq < 192, S < 96
+VD_FRAMES_HD uint32_t tb_lane_stage(uint32_t r0, uint32_t s, uint32_t S, uint32_t m16)
+{
+    const uint32_t x = r0 + s;
+    if (S >= kFrmGroup) return x - S < x ? x - S : x;
+    return x - pfrm_mul24(pfrm_mul24(x, m16) >> 16, S);
+}
+// byte offset of the two floats of frame stage t (< S) against the frame's resource: offset + 8 <= 8 S
+VD_FRAMES_HD uint32_t tb_offset(uint32_t t) { return 8u * t; }
+// ... of lane s of a group that does not wrap (g0 >= 26, g0 + 96 - 26 <= S): frame stage g0 - 26 + s
+VD_FRAMES_HD uint32_t tb_offset_inside(uint32_t g0, uint32_t s) { return 8u * (g0 - kFrmLead + s); }
+// the map as the kernel evaluates it: the offset of stage g0 + s of the extended stream
+VD_FRAMES_HD uint32_t tb_stage_offset(uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
+{
+    if (!tb_wrap_group(g0, S)) return tb_offset_inside(g0, s);
+    return tb_offset(tb_lane_stage(tb_group_r0(g0, S, rc.m32), s, S, rc.m16));
+}
+
+// The argument checks of vd_run_device_tb_frames (all VD_ERR_ARG): the message, or null when the arguments are
+// good; frame_args_error's rules (no pad value to form: the scale only has to be finite and > 0).
+inline const char* tb_args_error(uint64_t llr_addr, uint64_t llr_stride, uint64_t output_stride, uint64_t maxFrameBits,
+                                 int nframes, float scale)
+{
+    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
+    if (nframes < 1) return "nframes must be >= 1";
+    if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
+    if (llr_addr & 7) return "llr_d must be 8-byte aligned";
+    if ((llr_stride & 7) || (output_stride & 3)) return "llr_stride % 8 or output_stride % 4 != 0";
+    if (nframes > 1 && llr_stride < 8 * maxFrameBits) return "llr_stride smaller than 8 * maxFrameBits: frames would overlap";
+    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
+        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
+    return nullptr;
+}
+
 }  // namespace vd

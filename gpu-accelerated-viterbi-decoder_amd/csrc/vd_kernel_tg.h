@@ -47,6 +47,9 @@ constexpr int kPun = 16;
 // noise-free stages around the frame exist as a select in the loads (TgInFrm; vd_frames.h)
 constexpr int kFrm = 24;
 // kFrm + kPun + base = the kept float values of independent punctured frames, one frame per wave (TgInPfr)
+// kFrm + kTb + base = float channel values of independent tail-biting frames, one frame per wave: the stages
+// around the frame are the frame's own other end, a wrap in the loads (TgInTbf; vd_frames.h)
+constexpr int kTb = 32;
 
 template <int CH>
 struct TgFmt {
@@ -720,6 +723,48 @@ __device__ __forceinline__ float2 tg_pfr_load(__amdgpu_buffer_rsrc_t rs, const P
     return make_float2(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
 }
 
+// ---------------------------------------------------------------- tail-biting frames (vd_frames.h "tail-biting frames")
+// kFrm + kTb + base = the float values of independent tail-biting frames (every format), one frame per wave.  A
+// frame launch in everything but the loads and the pad (FRM: the wave's frame and length, its output words, the
+// fairness rule; no pad select, no segment machinery): stage p of the extended stream is frame stage (p - 26) mod
+// S, so every load lands inside the frame's resource of 8 S bytes and no lane relies on the range check.  The
+// wave divides once at set-up (tb_recip of its S, scalar registers).  A group head then takes one wave-uniform
+// branch (tb_wrap_group): a group inside the frame loads at 8 (p - 26) as TgInFrm does, minus the clamp; group 0
+// and the groups from the frame's end on reduce their first stage on the scalar unit (tb_group_r0) and each
+// lane's stage by a conditional subtract or, for S < 96, a 16-bit reciprocal (tb_lane_stage).  The offsets are
+// computed where the loads are issued, one group ahead of their use: nothing waits in a VGPR for a group.
+template <int BASE>
+struct TgInTbf : TgInLlr<BASE> {
+    static constexpr bool FRM = true;
+    static constexpr bool TBF = true;
+};
+template <> struct TgIn<kFrm + kTb + HARD> : TgInTbf<HARD> {};
+template <> struct TgIn<kFrm + kTb + SOFT4> : TgInTbf<SOFT4> {};
+template <> struct TgIn<kFrm + kTb + SOFT8> : TgInTbf<SOFT8> {};
+template <> struct TgIn<kFrm + kTb + SOFT16> : TgInTbf<SOFT16> {};
+template <> struct TgIn<kFrm + kTb + FP32> : TgInTbf<FP32> {};
+template <class T, class = void>
+struct HasTbf : std::false_type {};
+template <class T>
+struct HasTbf<T, std::void_t<decltype(T::TBF)>> : std::bool_constant<T::TBF> {};
+// the values of lane stages sa and sb (< 96) of the group from extended stage g0 (wave-uniform) of the tail-biting
+// frame of S stages (wave-uniform, with its reciprocals rc) whose resource is rs: one branch for both loads
+__device__ __forceinline__ void tg_tbf_load(__amdgpu_buffer_rsrc_t rs, uint32_t g0, uint32_t sa, uint32_t sb, uint32_t S,
+                                            const TbRecip& rc, float2& ra, float2& rb)
+{
+    uint32_t oa, ob;
+    if (tb_wrap_group(g0, S)) {
+        const uint32_t r0 = __builtin_amdgcn_readfirstlane(tb_group_r0(g0, S, rc.m32));
+        oa = tb_offset(tb_lane_stage(r0, sa, S, rc.m16));
+        ob = tb_offset(tb_lane_stage(r0, sb, S, rc.m16));
+    } else {
+        oa = tb_offset_inside(g0, sa);
+        ob = tb_offset_inside(g0, sb);
+    }
+    ra = TgIn<FP32>::template load<0>(rs, oa);
+    rb = TgIn<FP32>::template load<0>(rs, ob);
+}
+
 // ---------------------------------------------------------------- segment launches
 // A launch of 6400 chunks on 1024 SIMDs, one chunk per wave, puts 7 waves on a quarter of the SIMDs and
 // 6 on the rest, and the 7-wave SIMDs set the kernel time.  In a segment launch (Geom::seg) workgroup g
@@ -829,9 +874,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     // This wave's work: chunk blockIdx.x * kWaves + wv, or, in a segment launch (Geom::seg), segment wv of
     // the workgroup's chunks -- see "segment launches" above.
     // A batched launch (Geom::nbatch > 1) decodes chunk c of batch b at launch chunk b * nchunks + c.
-    // (a frame is never split: the punctured-frame kernels are compiled without the segment machinery, which
-    // otherwise costs the SOFT8 / M_B16 one a spilled VGPR)
-    const bool split = HasPfr<IN>::value ? false : geo.seg != nullptr;
+    // (a frame is never split: the punctured-frame and tail-biting kernels are compiled without the segment
+    // machinery, which otherwise costs the punctured SOFT8 / M_B16 one a spilled VGPR)
+    const bool split = HasPfr<IN>::value || HasTbf<IN>::value ? false : geo.seg != nullptr;
     const int piece = split ? wv : -1;
     const uint32_t gchunk = blockIdx.x * kWaves + wv;
     constexpr bool FRM = HasFrm<IN>::value;  // frame launch: this wave decodes frame gchunk whole (never split)
@@ -841,6 +886,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         const uint32_t n = geo.frmBits ? geo.frmBits[gchunk] : geo.frmMax;
         frmS = __builtin_amdgcn_readfirstlane(n < geo.frmMax ? n : geo.frmMax);
     }
+    constexpr bool TBF = HasTbf<IN>::value;  // ... a tail-biting frame: wrapped loads, no pad (tg_tbf_load)
     constexpr bool PFR = HasPfr<IN>::value;  // ... of the kept values of a punctured frame (tg_pfr_load)
     uint32_t pfrB = 0;                       // its received bytes (wave-uniform)
     if constexpr (PFR) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes(geo.pun, frmS));
@@ -872,6 +918,11 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         sw.W0 = words32(sw.c0);
         sw.W1 = sw.W2 = sw.W3 = 0u;
         if (sw.W0 == 0) return;  // an empty chunk (never in a segment launch: its chunks have >= kSplitMinWords words)
+    }
+    TbRecip tbr = {0u, 0u};  // tail-biting: the reciprocals of frmS >= 1 (wave-uniform; the one division of the wave)
+    if constexpr (TBF) {
+        const TbRecip rc = tb_recip(frmS);
+        tbr = {(uint32_t)__builtin_amdgcn_readfirstlane(rc.m32), (uint32_t)__builtin_amdgcn_readfirstlane(rc.m16)};
     }
     // this wave's segment [b0, b1) and the segments whose start is exact (a chunk start)
     const SegPos b0 = split ? seg_bound(sw, wv) : SegPos{0, 0u}, b1 = split ? seg_bound(sw, wv + 1) : SegPos{1, 0u};
@@ -968,6 +1019,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
         rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
         rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
+    } else if constexpr (TBF) {  // one resource for the whole frame: its 8 frmS bytes; group 0 wraps its lead
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(8u * frmS), 0x00020000);
+        tg_tbf_load(rs, 0u, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
     } else if constexpr (FRM) {  // one resource for the whole frame: its 8 frmS bytes (start = 0, j0 = 0)
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(8u * frmS), 0x00020000);
         rA = tg_frm_load(rs, (uint32_t)sA);
@@ -1129,7 +1183,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     for (uint32_t j = j0;; j += 3) {
         // group head: the table from the inputs loaded one group ago, the next group's loads, then the
         // fairness board (its load returns during this group; nothing here waits on it)
-        if constexpr (FRM) {
+        if constexpr (FRM && !TBF) {
             // the pad value in the lanes of this group's pad stages (vd_frames.h): a uniform branch that the
             // groups inside the frame skip
             const uint32_t g0 = 32u * j, end = frame_end(frmS, geo.frmTerm != 0);
@@ -1175,6 +1229,10 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             rs = tg_rsrc_pun(in, start + 32ull * (j + 3), availB, geo.pun, &r0);
             rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
             rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
+        } else if constexpr (TBF) {  // the next group's stages of the extended stream: the frame, wrapped
+            const uint32_t g0n = 32u * (j + 3);
+            __builtin_assume(g0n >= kFrmGroup);  // (no lead: tb_wrap_group and tb_group_r0 fold to their g0 >= 26 forms)
+            tg_tbf_load(rs, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
         } else if constexpr (FRM) {  // the next group's stages of the padded stream
             rA = tg_frm_load(rs, 32u * (j + 3) + (uint32_t)sA);
             rB = tg_frm_load(rs, 32u * (j + 3) + (uint32_t)sB);

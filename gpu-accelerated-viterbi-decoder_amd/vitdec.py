@@ -48,7 +48,7 @@ EXPORTS = ["vd_options_valid", "vd_input_size", "vd_message_len", "vd_output_siz
            "vd_split_cap_exits", "vd_set_guard_check", "vd_guard_violations", "vd_run_device_llr_batch", "vd_build_info",
            "vd_decoder_kernel_name", "vd_punctured_len", "vd_run_device_punct", "vd_run_device_punct_batch",
            "vd_run_punct", "vd_frame_output_size", "vd_run_device_frames", "vd_run_frames",
-           "vd_run_device_punct_frames", "vd_run_punct_frames"]
+           "vd_run_device_punct_frames", "vd_run_punct_frames", "vd_run_device_tb_frames", "vd_run_tb_frames"]
 
 # puncture patterns (period, keep0, keep1): bit i of keep0 / keep1 = the first (0171) / second (0133) encoder
 # output of the stages t with t % period == i is transmitted.  Any valid masks decode (and equal the rate-1/2
@@ -112,6 +112,8 @@ def lib():
            "vd_run_device_punct_frames": ([vp, vp, sz, vp, sz, vp, sz, i, i, f, i, ctypes.c_uint32, ctypes.c_uint32, vp], None),
            "vd_run_punct_frames": ([vp, vp, sz, vp, sz, vp, sz, i, i, f, i, ctypes.c_uint32, ctypes.c_uint32,
                                     ctypes.POINTER(f)], None),
+           "vd_run_device_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, vp], None),
+           "vd_run_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, ctypes.POINTER(f)], None),
            "vd_kernel_name": ([i], ctypes.c_char_p),
            "vd_decoder_kernel_name": ([vp, sz, i, i], ctypes.c_char_p)}
     for name, (args, res) in sig.items():
@@ -260,7 +262,8 @@ class ViterbiCUDA:
         """the kernel and launch form this decoder runs for nbatch batches of inputNum values
         (vd_decoder_kernel_name: follows VD_NO_PK / VD_PK_SPLIT / VD_NO_SPLIT as read at creation); llr: False /
         0 packed input, True / 1 float channel values, 2 punctured float values, 3 a frame launch (inputNum =
-        maxFrameBits, nbatch = nframes), 4 a launch of punctured frames (likewise)"""
+        maxFrameBits, nbatch = nframes), 4 a launch of punctured frames (likewise), 5 a launch of tail-biting
+        frames (likewise)"""
         return lib().vd_decoder_kernel_name(self._h, inputNum, nbatch, int(llr)).decode()
 
     def set_guard_check(self, enable=True):
@@ -425,6 +428,39 @@ class ViterbiCUDA:
                                                 maxFrameBits, nframes, 1 if terminated else 0, scale, *pattern,
                                                 ctypes.c_void_p(stream)))
 
+    # ---- tail-biting frames: the wrap-around of every frame in the frame launch's loads (vd_capi.h) ----
+    def run_tb_frames(self, llr_h, scale=40000.0, frame_bits=None):
+        """Blocking decode of nframes tail-biting frames in one launch.  llr_h: float array [nframes, 2 *
+        maxFrameBits], frame f in row f (first encoder output first, the encoder preloaded with the frame's last six
+        information bits); frame_bits: the stages of each frame as in run_frames.  Frame f equals, word for word,
+        the one-chunk decode of wrap_frame(its values).  Every format, HARD included.  Returns (out, ms) shaped as
+        run_frames does: bit i of a row (MSB first), i < S_f, is information bit i of the frame, the rest of its
+        last word decodes the wrap (frame bit i mod S_f)."""
+        llr_h = np.ascontiguousarray(llr_h, dtype=np.float32)
+        if llr_h.ndim != 2 or llr_h.shape[1] % 2:
+            raise VitdecError("run_tb_frames: llr_h must be [nframes, 2 * maxFrameBits]")
+        nframes, max_bits = llr_h.shape[0], llr_h.shape[1] // 2
+        row = frame_output_size(self.options, max_bits)
+        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
+        fb = None
+        if frame_bits is not None:
+            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
+            if fb.shape != (nframes,):
+                raise VitdecError("run_tb_frames: frame_bits must hold one length per frame")
+        ms = ctypes.c_float(0.0)
+        _check(lib().vd_run_tb_frames(self._h, llr_h.ctypes.data, 8 * max_bits, out.ctypes.data, row,
+                                      fb.ctypes.data if fb is not None else None, max_bits, nframes, scale,
+                                      ctypes.byref(ms)))
+        return out, ms.value
+
+    def run_device_tb_frames(self, llr_ptr, llr_stride, output_ptr, output_stride, maxFrameBits, nframes, scale=40000.0,
+                             frame_bits_ptr=0, stream=0):
+        """Async decode of nframes tail-biting frames in one launch (vd_run_device_tb_frames): pointers, strides and
+        lengths as run_device_frames; frame f reads exactly its 2 S_f floats and writes 4 * ceil(S_f / 32) bytes."""
+        _check(lib().vd_run_device_tb_frames(self._h, ctypes.c_void_p(llr_ptr), llr_stride, ctypes.c_void_p(output_ptr),
+                                             output_stride, ctypes.c_void_p(frame_bits_ptr) if frame_bits_ptr else None,
+                                             maxFrameBits, nframes, scale, ctypes.c_void_p(stream)))
+
 
 class PinnedArray:
     """A numpy view of page-locked host memory from vd_host_alloc (freed with the object)."""
@@ -514,6 +550,22 @@ def pad_frame(values, terminated, scale, opt):
     out[:2 * FRAME_LEAD] = pad
     out[2 * FRAME_LEAD:2 * (FRAME_LEAD + S)] = v
     return out
+
+
+def wrap_frame(values):
+    """The extended stream that defines a tail-biting frame decode (host helper; the contract the tests feed to
+    the oracle).
+
+    values: the 2 S floats of a tail-biting frame of S >= 1 stages.  Returns the 2 P floats, P = 64 + 32 ceil(S /
+    32), with stage p holding both values of frame stage (p - 26) mod S (the non-negative residue, as many turns
+    as P takes); the frame decode equals the one-chunk decode (nchunks = 1, inputNum = 2 P) of its
+    SoftDecisionPacker(opt, scale) packing, and decoded bit i < S is information bit i of the frame."""
+    v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+    if v.size % 2 or v.size == 0:
+        raise VitdecError("wrap_frame: two values per stage, at least one stage")
+    S = v.size // 2
+    P = 64 + 32 * ((S + 31) // 32)
+    return v.reshape(S, 2)[(np.arange(P) - FRAME_LEAD) % S].reshape(-1).copy()
 
 
 def simulate_host(options, n_bits, snr, bit_seed, noise_seed):

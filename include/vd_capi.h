@@ -179,8 +179,9 @@ int vd_run_punct(vd_decoder* dec, const float* rx_h, void* output_h, size_t inpu
  * decodes one frame, and all frames go in one launch.  Every format and metric; an open frame needs a neutral
  * code, so a HARD decoder with terminated = 0 gets VD_ERR_OPTIONS.  VD_ERR_ARG: maxFrameBits outside
  * [1, 2^20], nframes < 1, scale not finite and > 0, a misaligned pointer or stride, overlapping frames.
- * Punctured frames: vd_run_device_punct_frames below.  Packed-word frames, frames longer than 2^20 stages,
- * tail-biting and vd_decode_pk twins of the frame kernels are not supported. */
+ * Punctured frames: vd_run_device_punct_frames below; tail-biting frames: vd_run_device_tb_frames below.
+ * Packed-word frames, frames longer than 2^20 stages, punctured tail-biting frames and vd_decode_pk twins of the
+ * frame kernels are not supported. */
 
 /* bytes a frame of frameBits stages decodes to: 4 * ceil(frameBits / 32), for O_B32 and O_B16 alike */
 size_t vd_frame_output_size(int options, size_t frameBits);
@@ -231,6 +232,40 @@ int vd_run_device_punct_frames(vd_decoder* dec, const float* rx_d, size_t rx_str
 int vd_run_punct_frames(vd_decoder* dec, const float* rx_h, size_t rx_stride, void* output_h, size_t output_stride,
                         const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int terminated, float scale,
                         int period, uint32_t keep0, uint32_t keep1, float* kernel_ms);
+
+/* ---- tail-biting frames (new: packets whose encoder starts in the state it ends in, e.g. 802.16 OFDMA's
+ *      convolutional code and many short control and burst formats) ----
+ * A tail-biting frame is S >= 1 trellis stages, 2 S float channel values, first encoder output first.  The encoder's
+ * register at the first stage holds the frame's last six information bits (cyclically for S < 6), so output stage
+ * t depends on information bits t, t - 1, ..., t - 6, all taken mod S; no tail is sent.  With W = ceil(S / 32) and
+ * P = 64 + 32 W, the frame's extended stream has P stages, and stage p holds both values of frame stage
+ * (p - 26) mod S: the non-negative residue, the wrap continuing for as many turns as P needs (S = 1: every stage
+ * is the frame's one stage); the same rule defines anything the kernel prefetches beyond P.  The decode equals,
+ * word for word, the one-chunk decode (inputNum = 2 P, nchunks = 1, O_B16 policy 0) of the SoftDecisionPacker(
+ * options, scale) packing of the extended stream.  It writes W 32-bit words (O_B16: 2 W 16-bit words); decoded
+ * bit i (MSB first) with i < S is information bit i, and the remaining bits of the last word decode the wrap
+ * (frame bit i mod S).  One pass with the reference's fixed window (26 warm-up stages from equal metrics, 38
+ * traceback stages): the extended stream is the interior of a periodic stream, and the window decodes it as it
+ * decodes the interior of any stream; no iterations, no search over start states.  No pad stages and no
+ * erasures, so every format and metric is supported, HARD included.  The extended stream is never stored: the
+ * wrap-around sits in the loads of the branch-metric table build, one wave decodes one frame, all frames go in
+ * one launch.  Punctured tail-biting frames are not supported yet: until then a caller depunctures them into
+ * 2 S floats (+0.0f at the punctured positions; not for HARD decoders). */
+
+/* nframes tail-biting frames in one launch, under the rules of vd_run_device_frames (asynchronous, no allocation,
+ * capturable, the stream on the decoder's device; the same pointers, strides and lengths array, no terminated
+ * argument).  Frame f reads exactly its 2 S_f floats at llr_d + f * llr_stride bytes and writes exactly
+ * vd_frame_output_size(S_f) bytes at output_d + f * output_stride bytes, S_f = min(frame_bits_d[f], maxFrameBits),
+ * or maxFrameBits when frame_bits_d is NULL; S_f = 0 writes nothing.  VD_ERR_ARG: maxFrameBits outside [1, 2^20],
+ * nframes < 1, scale not finite and > 0, llr_d not 8-byte aligned, llr_stride % 8 or output_stride % 4, and with
+ * nframes > 1 llr_stride < 8 * maxFrameBits or output_stride < vd_frame_output_size(maxFrameBits). */
+int vd_run_device_tb_frames(vd_decoder* dec, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
+                            const uint32_t* frame_bits_d /* device, or NULL: every frame has maxFrameBits */,
+                            size_t maxFrameBits, int nframes, float scale, void* stream);
+/* Blocking host-to-host variant over host buffers of the same layout (H2D, the launch, D2H); the output bytes
+ * no frame writes keep their values.  kernel_ms as in vd_run. */
+int vd_run_tb_frames(vd_decoder* dec, const float* llr_h, size_t llr_stride, void* output_h, size_t output_stride,
+                     const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, float scale, float* kernel_ms);
 
 /* ---- the reference harness's channel source (RandBitGen | ConvolutionalEncoder | AddNoise |
  *      SoftDecisionPacker, viterbiDF.h:20-167), host and GPU ---- */
@@ -284,7 +319,8 @@ const char* vd_kernel_name(int options);
  * VD_NO_SPLIT); "-" when such a decode launches nothing (fewer than one output word; llr 2 on a HARD
  * decoder); llr 3: the frame launch of vd_run_device_frames (vd_decode_tg<FRM+...>), with inputNum =
  * maxFrameBits and nbatch = nframes; llr 4: the launch of vd_run_device_punct_frames (vd_decode_tg<FRM+PUN+...>),
- * inputNum and nbatch as for llr 3, "-" on a HARD decoder; valid until the thread's next call */
+ * inputNum and nbatch as for llr 3, "-" on a HARD decoder; llr 5: the launch of vd_run_device_tb_frames
+ * (vd_decode_tg<FRM+TB+...>), inputNum and nbatch as for llr 3; valid until the thread's next call */
 const char* vd_decoder_kernel_name(vd_decoder* dec, size_t inputNum, int nbatch, int llr);
 /* build record: "<16 hex digits of the SHA-256 of the concatenated sources> <their paths, relative to the
  * package directory>"; the Python binding refuses a library whose sources have changed since (stale build) */
