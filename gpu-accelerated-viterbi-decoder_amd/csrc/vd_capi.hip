@@ -261,7 +261,8 @@ const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, i
     if (!d || nbatch < 1) return "-";
     if (llr == 2 && ch_of(d->options) == HARD) return "-";  // no punctured HARD kernels
     if (llr == 4 && ch_of(d->options) == HARD) return "-";  // ... nor punctured HARD frames
-    if (llr == 3 || llr == 4 || llr == 5) {  // a frame launch (4: of punctured, 5: of tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
+    if (llr == 6 && ch_of(d->options) == HARD) return "-";  // ... nor punctured tail-biting HARD frames
+    if (llr == 3 || llr == 4 || llr == 5 || llr == 6) {  // a frame launch (4: of punctured, 5: of tail-biting, 6: of punctured tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
         if (inputNum < 1 || inputNum > kFrmMaxBits) return "-";
         name = plan_name(plan_frames(d->options, (uint64_t)nbatch), d->options, llr);
         return name.c_str();
@@ -570,14 +571,15 @@ static int frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, 
 }
 
 // the one launch of checked arguments; pun: the frames hold the kept values of punctured frames, tb: the frames
-// are tail-biting (no pad: terminated means nothing) (vd_frames.h)
+// are tail-biting (no pad: terminated means nothing), both: punctured tail-biting frames (vd_frames.h)
 static int launch_frames_checked(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
                                  const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
                                  hipStream_t s, const Punct* pun = nullptr, bool tb = false)
 {
     const int options = d->options;
     const LaunchPlan p = plan_frames(options, (uint64_t)nframes);
-    launch_fn f = tb    ? launcher_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
+    launch_fn f = tb && pun ? launcher_punct_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
+                  : tb  ? launcher_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                   : pun ? launcher_punct_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                         : launcher_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1);
     if (!f || !p.launches) return fail(VD_ERR_OPTIONS, "invalid options");
@@ -765,6 +767,69 @@ int vd_run_tb_frames(vd_decoder* d, const float* llr_h, size_t llr_stride, void*
     VD_HIP(hipEventRecord(d->ev0, d->stream));
     rc = launch_frames_checked(d, (const float*)d->llr_d, llr_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes, 0,
                                scale, d->stream, nullptr, true);
+    if (rc != VD_OK) return rc;
+    VD_HIP(hipEventRecord(d->ev1, d->stream));
+    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
+    VD_HIP(hipStreamSynchronize(d->stream));
+    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    return VD_OK;
+}
+
+// ---- punctured tail-biting frames (vd_frames.h "punctured tail-biting frames"; vd_decode_tg<FRM+TB+PUN+...>) ----
+// the argument checks of a punctured tail-biting frame decode: VD_ERR_ARG / VD_ERR_OPTIONS, or *pn filled in
+static int punct_tb_frames_args(const vd_decoder* d, const void* rx, size_t rx_stride, const void* output, size_t output_stride,
+                                size_t maxFrameBits, int nframes, float scale, int period, uint32_t keep0, uint32_t keep1,
+                                bool device, Punct* pn)
+{
+    if (!d || !rx || !output) return fail(VD_ERR_ARG, "null argument");
+    if (const char* why = ptb_args_error(device ? (uint64_t)(uintptr_t)rx : 0, rx_stride, output_stride, maxFrameBits, nframes,
+                                         scale, period, keep0, keep1))
+        return fail(VD_ERR_ARG, why);
+    if (ch_of(d->options) == HARD)
+        return fail(VD_ERR_OPTIONS, "punctured tail-biting frames on a HARD decoder: a punctured value must decode as code 0 = "
+                                    "value 0, and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");
+    *pn = punct_make(period, keep0, keep1);
+    return VD_OK;
+}
+
+int vd_run_device_punct_tb_frames(vd_decoder* d, const float* rx_d, size_t rx_stride, void* output_d, size_t output_stride,
+                                  const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, float scale, int period,
+                                  uint32_t keep0, uint32_t keep1, void* stream)
+{
+    Punct pn;
+    int rc = punct_tb_frames_args(d, rx_d, rx_stride, output_d, output_stride, maxFrameBits, nframes, scale, period, keep0, keep1,
+                                  true, &pn);
+    if (rc != VD_OK) return rc;
+    return launch_frames_checked(d, rx_d, rx_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes, 0, scale,
+                                 (hipStream_t)stream, &pn, true);
+}
+
+// the host buffers laid out like the device ones (vd_run_punct_frames): the last frame's part ends with the
+// received values of its maxFrameBits stages
+int vd_run_punct_tb_frames(vd_decoder* d, const float* rx_h, size_t rx_stride, void* output_h, size_t output_stride,
+                           const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, float scale, int period,
+                           uint32_t keep0, uint32_t keep1, float* kernel_ms)
+{
+    Punct pn;
+    int rc = punct_tb_frames_args(d, rx_h, rx_stride, output_h, output_stride, maxFrameBits, nframes, scale, period, keep0, keep1,
+                                  false, &pn);
+    if (rc != VD_OK) return rc;
+    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
+    const size_t inB = (size_t)(nframes - 1) * rx_stride + pfrm_bytes(pn, (uint32_t)maxFrameBits);
+    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
+    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
+    VD_HIP(hipSetDevice(d->device));
+    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
+    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
+    if (rc != VD_OK) return rc;
+    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
+    if (inB) VD_HIP(hipMemcpyAsync(d->llr_d, rx_h, inB, hipMemcpyHostToDevice, d->stream));
+    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
+    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
+    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
+    VD_HIP(hipEventRecord(d->ev0, d->stream));
+    rc = launch_frames_checked(d, (const float*)d->llr_d, rx_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes, 0,
+                               scale, d->stream, &pn, true);
     if (rc != VD_OK) return rc;
     VD_HIP(hipEventRecord(d->ev1, d->stream));
     VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));

@@ -209,11 +209,13 @@ VD_FRAMES_HD uint32_t tb_group_r0(uint32_t g0, uint32_t S, uint32_t m32)
 // frame stage of lane s (< kFrmGroup) of a wrapping group: (r0 + s) mod S, r0 < S.  x = r0 + s < S + 96: for
 // S >= 96 that is below 2 S, one conditional subtract (as a minimum: no select); for S < 96, x < 192 and the
 // 16-bit reciprocal is exact (above), in 24-bit products: x < 192, m16 <= 65537, x m16 < 2^24, dq < 192, S < 96
+// (tb_turns_stage: that form alone, for a caller that knows S < 96)
+VD_FRAMES_HD uint32_t tb_turns_stage(uint32_t x, uint32_t S, uint32_t m16) { return x - pfrm_mul24(pfrm_mul24(x, m16) >> 16, S); }
 VD_FRAMES_HD uint32_t tb_lane_stage(uint32_t r0, uint32_t s, uint32_t S, uint32_t m16)
 {
     const uint32_t x = r0 + s;
     if (S >= kFrmGroup) return x - S < x ? x - S : x;
-    return x - pfrm_mul24(pfrm_mul24(x, m16) >> 16, S);
+    return tb_turns_stage(x, S, m16);
 }
 // byte offset of the two floats of frame stage t (< S) against the frame's resource: offset + 8 <= 8 S
 VD_FRAMES_HD uint32_t tb_offset(uint32_t t) { return 8u * t; }
@@ -237,6 +239,94 @@ inline const char* tb_args_error(uint64_t llr_addr, uint64_t llr_stride, uint64_
     if (llr_addr & 7) return "llr_d must be 8-byte aligned";
     if ((llr_stride & 7) || (output_stride & 3)) return "llr_stride % 8 or output_stride % 4 != 0";
     if (nframes > 1 && llr_stride < 8 * maxFrameBits) return "llr_stride smaller than 8 * maxFrameBits: frames would overlap";
+    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
+        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- punctured tail-biting frames (channel ids kFrm + kTb + kPun + format)
+// A punctured tail-biting frame of S >= 1 stages under a pattern holds the punct_len(2 S) kept values of its 2 S
+// mother-code values, and the pattern's phase belongs to the frame stage: stage p of the extended stream is frame
+// stage t = (p - 26) mod S and uses bit t % period, so the phase restarts at every wrap, whether or not the period
+// divides S.  Its decode is the tail-biting decode above of the depunctured frame (+0.0f at the punctured
+// positions).  One resource per frame over its pfrm_bytes, and per 96-stage group one of three wave-uniform forms
+// (ptb_group), each ending in pfrm_offsets:
+//   inside (no lane wraps: g0 >= 26, g0 + 96 - 26 <= S): the punctured-frame path, (base4, r0) of frame stage
+//     g0 - 26 by pfrm_base and lane stage s;
+//   one wrap (S >= 96: x = rs + s < S + 96 <= 2 S with rs = (g0 - 26) mod S): the lanes with x < S are frame stages
+//     rs + s on the pair (base4, r0) of rs, the others frame stages x - S < 96 counted from frame stage 0: the
+//     pair (0, 0) and lane stage x - S, a select per lane between two uniform pairs;
+//   turns (S < 96): t = (rs + s) mod S by the 16-bit reciprocal (tb_lane_stage's argument), the pair (0, 0) and
+//     lane stage t < 96.
+// pfrm_offsets' argument x = r0 + lane stage < 16 + 96 holds in all three.  Every stage is a frame stage < S, so a
+// kept value's offset lies inside the range (offset + 4 <= pfrm_bytes) and nothing is "past the frame's end"; a
+// punctured value takes kFrmOutside (every kept offset stays below 2^24: no 32-bit wrap of offset + 4) and loads
+// zero through the range check, the one thing the range check is relied on for.  A frame with no kept value has a
+// range of 0 bytes and reads nothing.  tests/cxx/ptb_frames_check.cpp checks the helpers below against a plain
+// enumeration.
+
+// wave-uniform values stay in scalar registers in the kernel (a no-op on values already scalar)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define VD_FRAMES_UNIFORM(x) ((uint32_t)__builtin_amdgcn_readfirstlane(x))
+#else
+#define VD_FRAMES_UNIFORM(x) ((uint32_t)(x))
+#endif
+constexpr uint32_t kPtbInside = 0, kPtbWrap = 1, kPtbTurns = 2;
+// the uniform part of the 96-stage group from extended stage g0 (a multiple of kFrmGroup; <= kFrmMaxBits + a few
+// groups) of a frame of S stages with the reciprocals rc: its form, the frame stage rs of its lane 0 (wrapping
+// forms) and the pair (base4, r0) of its first frame stage (inside, one wrap)
+struct PtbGroup {
+    uint32_t mode, rs, base4, r0;
+};
+VD_FRAMES_HD PtbGroup ptb_group(const Punct& pn, uint32_t g0, uint32_t S, const TbRecip& rc)
+{
+    PtbGroup g = {kPtbTurns, 0u, 0u, 0u};
+    const bool wrap = tb_wrap_group(g0, S);
+    if (wrap) g.rs = VD_FRAMES_UNIFORM(tb_group_r0(g0, S, rc.m32));
+    if (wrap && S < kFrmGroup) return g;
+    g.mode = wrap ? kPtbWrap : kPtbInside;
+    uint32_t r0;
+    g.base4 = VD_FRAMES_UNIFORM(pfrm_base(pn, VD_FRAMES_UNIFORM(wrap ? g.rs : g0 - kFrmLead), &r0));
+    g.r0 = VD_FRAMES_UNIFORM(r0);
+    return g;
+}
+#undef VD_FRAMES_UNIFORM
+// the byte offsets of the two values of lane s (< kFrmGroup) of the group g against the frame's resource: inside
+// the range exactly for a kept value (m16: tb_recip(S).m16, used for S < 96 only)
+VD_FRAMES_HD PfrmOff ptb_offsets(const Punct& pn, const PtbGroup& g, uint32_t s, uint32_t S, uint32_t m16)
+{
+    uint32_t b = g.base4, r = g.r0, ls = s;
+    if (g.mode == kPtbWrap) {
+        const uint32_t x = g.rs + s;  // < S + 96 <= 2 S: at most one wrap point in the group
+        if (x >= S) {                 // counted from frame stage 0: x - S <= rs - S + 95 < 95
+            b = 0u;
+            r = 0u;
+            ls = x - S;
+        }
+    } else if (g.mode == kPtbTurns) {
+        ls = tb_turns_stage(g.rs + s, S, m16);  // tb_lane_stage for S < 96 (ptb_group): t < 96; b = r = 0
+    }
+    return pfrm_offsets(pn, b, r, 0u, ls);
+}
+// the map as the kernel evaluates it: the offsets of the two values of stage g0 + s of the extended stream
+VD_FRAMES_HD PfrmOff ptb_stage_offsets(const Punct& pn, uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
+{
+    return ptb_offsets(pn, ptb_group(pn, g0, S, rc), s, S, rc.m16);
+}
+
+// The argument checks of vd_run_device_punct_tb_frames (all VD_ERR_ARG): the message, or null when the arguments
+// are good; pfrm_args_error's rules with tb_args_error's scale rule (no pad value to form).
+inline const char* ptb_args_error(uint64_t rx_addr, uint64_t rx_stride, uint64_t output_stride, uint64_t maxFrameBits,
+                                  int nframes, float scale, int period, uint32_t keep0, uint32_t keep1)
+{
+    if (!punct_valid(period, keep0, keep1))
+        return "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
+    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
+    if (nframes < 1) return "nframes must be >= 1";
+    if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
+    if ((rx_addr | rx_stride | output_stride) & 3) return "rx_d, rx_stride and output_stride must be multiples of 4 bytes";
+    if (nframes > 1 && rx_stride < pfrm_bytes(punct_make(period, keep0, keep1), (uint32_t)maxFrameBits))
+        return "rx_stride smaller than 4 * vd_punctured_len(2 * maxFrameBits): frames would overlap";
     if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
         return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
     return nullptr;

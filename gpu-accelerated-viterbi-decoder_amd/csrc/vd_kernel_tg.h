@@ -49,6 +49,7 @@ constexpr int kFrm = 24;
 // kFrm + kPun + base = the kept float values of independent punctured frames, one frame per wave (TgInPfr)
 // kFrm + kTb + base = float channel values of independent tail-biting frames, one frame per wave: the stages
 // around the frame are the frame's own other end, a wrap in the loads (TgInTbf; vd_frames.h)
+// kFrm + kTb + kPun + base = the kept float values of independent punctured tail-biting frames (TgInPtb)
 constexpr int kTb = 32;
 
 template <int CH>
@@ -765,6 +766,43 @@ __device__ __forceinline__ void tg_tbf_load(__amdgpu_buffer_rsrc_t rs, uint32_t 
     rb = TgIn<FP32>::template load<0>(rs, ob);
 }
 
+// ---------------------------------------------------------------- punctured tail-biting frames (vd_frames.h)
+// kFrm + kTb + kPun + base = the kept float values of independent punctured tail-biting frames (SOFT4 .. FP32), one
+// frame per wave.  A frame launch in everything but the loads and the pad (FRM; no pad select, no segment
+// machinery), and the loads compose TgInTbf's wrap with TgInPfr's index map: one resource per frame over its
+// received bytes (pfrm_bytes, once per wave on the scalar unit), the wave's reciprocals of S from set-up, and per
+// group head one wave-uniform form (ptb_group: inside the frame, one wrap point, or several turns for S < 96) with
+// its scalar (rs, 4 q0 Kp, r0); per lane two single-dword loads at the vector offsets of ptb_offsets.  The
+// pattern's phase is the frame stage's, so it restarts at every wrap.  Punctured values read zero through the range
+// check (kFrmOutside); every kept offset lies inside the range.  The offsets are computed where the loads are
+// issued, one group ahead of their use: no flag waits in a VGPR.
+template <int BASE>
+struct TgInPtb : TgInLlr<BASE> {
+    static_assert(BASE != HARD, "HARD has no neutral code for an erasure");
+    static constexpr bool FRM = true;
+    static constexpr bool PTB = true;
+};
+template <> struct TgIn<kFrm + kTb + kPun + SOFT4> : TgInPtb<SOFT4> {};
+template <> struct TgIn<kFrm + kTb + kPun + SOFT8> : TgInPtb<SOFT8> {};
+template <> struct TgIn<kFrm + kTb + kPun + SOFT16> : TgInPtb<SOFT16> {};
+template <> struct TgIn<kFrm + kTb + kPun + FP32> : TgInPtb<FP32> {};
+template <class T, class = void>
+struct HasPtb : std::false_type {};
+template <class T>
+struct HasPtb<T, std::void_t<decltype(T::PTB)>> : std::bool_constant<T::PTB> {};
+// the values of lane stages sa and sb (< 96) of the group from extended stage g0 (wave-uniform) of the punctured
+// tail-biting frame of S stages (wave-uniform, with its reciprocals rc) whose resource is rs: one form for both
+__device__ __forceinline__ void tg_ptb_load(__amdgpu_buffer_rsrc_t rs, const Punct& pn, uint32_t g0, uint32_t sa, uint32_t sb,
+                                            uint32_t S, const TbRecip& rc, float2& ra, float2& rb)
+{
+    const PtbGroup g = ptb_group(pn, g0, S, rc);
+    const PfrmOff oa = ptb_offsets(pn, g, sa, S, rc.m16), ob = ptb_offsets(pn, g, sb, S, rc.m16);
+    const uint32_t xa = __builtin_amdgcn_raw_buffer_load_b32(rs, oa.o0, 0, 0), ya = __builtin_amdgcn_raw_buffer_load_b32(rs, oa.o1, 0, 0);
+    const uint32_t xb = __builtin_amdgcn_raw_buffer_load_b32(rs, ob.o0, 0, 0), yb = __builtin_amdgcn_raw_buffer_load_b32(rs, ob.o1, 0, 0);
+    ra = make_float2(__builtin_bit_cast(float, xa), __builtin_bit_cast(float, ya));
+    rb = make_float2(__builtin_bit_cast(float, xb), __builtin_bit_cast(float, yb));
+}
+
 // ---------------------------------------------------------------- segment launches
 // A launch of 6400 chunks on 1024 SIMDs, one chunk per wave, puts 7 waves on a quarter of the SIMDs and
 // 6 on the rest, and the 7-wave SIMDs set the kernel time.  In a segment launch (Geom::seg) workgroup g
@@ -874,9 +912,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     // This wave's work: chunk blockIdx.x * kWaves + wv, or, in a segment launch (Geom::seg), segment wv of
     // the workgroup's chunks -- see "segment launches" above.
     // A batched launch (Geom::nbatch > 1) decodes chunk c of batch b at launch chunk b * nchunks + c.
-    // (a frame is never split: the punctured-frame and tail-biting kernels are compiled without the segment
-    // machinery, which otherwise costs the punctured SOFT8 / M_B16 one a spilled VGPR)
-    const bool split = HasPfr<IN>::value || HasTbf<IN>::value ? false : geo.seg != nullptr;
+    // (a frame is never split: the punctured-frame, tail-biting and punctured tail-biting kernels are compiled
+    // without the segment machinery, which otherwise costs the punctured SOFT8 / M_B16 one a spilled VGPR)
+    const bool split = HasPfr<IN>::value || HasTbf<IN>::value || HasPtb<IN>::value ? false : geo.seg != nullptr;
     const int piece = split ? wv : -1;
     const uint32_t gchunk = blockIdx.x * kWaves + wv;
     constexpr bool FRM = HasFrm<IN>::value;  // frame launch: this wave decodes frame gchunk whole (never split)
@@ -888,8 +926,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     }
     constexpr bool TBF = HasTbf<IN>::value;  // ... a tail-biting frame: wrapped loads, no pad (tg_tbf_load)
     constexpr bool PFR = HasPfr<IN>::value;  // ... of the kept values of a punctured frame (tg_pfr_load)
+    constexpr bool PTB = HasPtb<IN>::value;  // ... of a punctured tail-biting frame: both maps (tg_ptb_load)
     uint32_t pfrB = 0;                       // its received bytes (wave-uniform)
-    if constexpr (PFR) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes(geo.pun, frmS));
+    if constexpr (PFR || PTB) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes(geo.pun, frmS));
     const uint32_t batch = FRM ? gchunk : geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
     const void* const in = (const char*)in_all + batch * geo.inStride;
     void* const out = (char*)out_all + batch * geo.outStride;
@@ -920,7 +959,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         if (sw.W0 == 0) return;  // an empty chunk (never in a segment launch: its chunks have >= kSplitMinWords words)
     }
     TbRecip tbr = {0u, 0u};  // tail-biting: the reciprocals of frmS >= 1 (wave-uniform; the one division of the wave)
-    if constexpr (TBF) {
+    if constexpr (TBF || PTB) {
         const TbRecip rc = tb_recip(frmS);
         tbr = {(uint32_t)__builtin_amdgcn_readfirstlane(rc.m32), (uint32_t)__builtin_amdgcn_readfirstlane(rc.m16)};
     }
@@ -1014,6 +1053,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         static_assert(pg.t0 == 0, "group 0 starts at frame stage 0: q0 = r0 = 0");
         rA = tg_pfr_load(rs, geo.pun, 0u, 0u, pg.lead, (uint32_t)sA);
         rB = tg_pfr_load(rs, geo.pun, 0u, 0u, pg.lead, (uint32_t)sB);
+    } else if constexpr (PTB) {  // one resource for the whole frame: its received bytes; group 0 wraps its lead
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)pfrB, 0x00020000);
+        tg_ptb_load(rs, geo.pun, 0u, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
     } else if constexpr (PUN) {
         uint32_t r0;
         rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
@@ -1183,7 +1225,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     for (uint32_t j = j0;; j += 3) {
         // group head: the table from the inputs loaded one group ago, the next group's loads, then the
         // fairness board (its load returns during this group; nothing here waits on it)
-        if constexpr (FRM && !TBF) {
+        if constexpr (FRM && !TBF && !PTB) {
             // the pad value in the lanes of this group's pad stages (vd_frames.h): a uniform branch that the
             // groups inside the frame skip
             const uint32_t g0 = 32u * j, end = frame_end(frmS, geo.frmTerm != 0);
@@ -1224,6 +1266,10 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             r0 = __builtin_amdgcn_readfirstlane(r0);
             rA = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sA);
             rB = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sB);
+        } else if constexpr (PTB) {  // the next group's kept values of the extended stream: the frame, wrapped
+            const uint32_t g0n = 32u * (j + 3);
+            __builtin_assume(g0n >= kFrmGroup);  // (no lead: tb_wrap_group and tb_group_r0 fold to their g0 >= 26 forms)
+            tg_ptb_load(rs, geo.pun, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
         } else if constexpr (PUN) {  // the next group's received values, at the offsets of its own r0
             uint32_t r0;
             rs = tg_rsrc_pun(in, start + 32ull * (j + 3), availB, geo.pun, &r0);

@@ -200,6 +200,26 @@ typename L::fn launcher_tb_frames(int ch, int me, bool o16)
     return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
 }
 
+// Punctured tail-biting frames (channel ids kFrm + kTb + kPun + format, vd_kernel_tg.h; vd_frames.h): the frame
+// launch with both index maps in its loads, the 9 punctured pairs x {O32, O16}, planned by plan_frames.
+template <class L>
+typename L::fn launcher_punct_tb_frames(int ch, int me, bool o16)
+{
+    struct Table {
+        typename L::fn at[5][3][2] = {};
+        Table()
+        {
+#define VD_X(C, M)                                                   \
+    at[C][M][0] = &L::template tg<kFrm + kTb + kPun + C, M, 32>;     \
+    at[C][M][1] = &L::template tg<kFrm + kTb + kPun + C, M, 16>;
+            VD_PUN_PAIRS(VD_X)
+#undef VD_X
+        }
+    };
+    static const Table t;
+    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
+}
+
 // ---------------------------------------------------------------- the knobs (read once, at vd_create)
 struct Knobs {
     int split = 1;    // segment launches: 0 none (VD_NO_SPLIT=1), 1 pieces, 2 thirds, 3 sevenths (VD_SPLIT=...)
@@ -298,14 +318,15 @@ inline constexpr const char* kCoreNames[3] = {"B32", "B16", "F16"};
 
 // vd_decoder_kernel_name: the kernel and launch form of one planned launch; input: 0 packed words, 1 float
 // channel values (LLR), 2 punctured float values (PUN), 3 frames of float values (FRM; a plan of plan_frames),
-// 4 punctured frames (FRM+PUN; a plan of plan_frames), 5 tail-biting frames (FRM+TB; a plan of plan_frames)
+// 4 punctured frames (FRM+PUN; a plan of plan_frames), 5 tail-biting frames (FRM+TB; a plan of plan_frames),
+// 6 punctured tail-biting frames (FRM+TB+PUN; a plan of plan_frames)
 inline std::string plan_name(const LaunchPlan& p, int o, int input)
 {
     if (!p.launches) return "-";
-    const std::string args = std::string(input == 5 ? "FRM+TB+" : input == 4 ? "FRM+PUN+" : input == 3 ? "FRM+" : input == 2 ? "PUN+" :
-                                         input ? "LLR+" : "") +
+    const std::string args = std::string(input == 6 ? "FRM+TB+PUN+" : input == 5 ? "FRM+TB+" : input == 4 ? "FRM+PUN+" :
+                                         input == 3 ? "FRM+" : input == 2 ? "PUN+" : input ? "LLR+" : "") +
                              kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," + (out_of(o) ? "O16" : "O32") + ">";
-    if (input == 3 || input == 4 || input == 5)
+    if (input == 3 || input == 4 || input == 5 || input == 6)
         return "vd_decode_tg<" + args + " one frame per wave, " + (ch_of(o) == SOFT16 ? "int32 tagged patterns" : "fp32 tagged core");
     if (p.form == Form::PkBatched) return "vd_decode_pk<" + args + " batched: two chunks per wave, int16 halves";
     if (p.form == Form::PkSplit) return "vd_decode_pk<" + args + " split: one chunk per wave cut in two, int16 halves";

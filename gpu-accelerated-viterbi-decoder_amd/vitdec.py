@@ -48,7 +48,8 @@ EXPORTS = ["vd_options_valid", "vd_input_size", "vd_message_len", "vd_output_siz
            "vd_split_cap_exits", "vd_set_guard_check", "vd_guard_violations", "vd_run_device_llr_batch", "vd_build_info",
            "vd_decoder_kernel_name", "vd_punctured_len", "vd_run_device_punct", "vd_run_device_punct_batch",
            "vd_run_punct", "vd_frame_output_size", "vd_run_device_frames", "vd_run_frames",
-           "vd_run_device_punct_frames", "vd_run_punct_frames", "vd_run_device_tb_frames", "vd_run_tb_frames"]
+           "vd_run_device_punct_frames", "vd_run_punct_frames", "vd_run_device_tb_frames", "vd_run_tb_frames",
+           "vd_run_device_punct_tb_frames", "vd_run_punct_tb_frames"]
 
 # puncture patterns (period, keep0, keep1): bit i of keep0 / keep1 = the first (0171) / second (0133) encoder
 # output of the stages t with t % period == i is transmitted.  Any valid masks decode (and equal the rate-1/2
@@ -114,6 +115,9 @@ def lib():
                                     ctypes.POINTER(f)], None),
            "vd_run_device_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, vp], None),
            "vd_run_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, ctypes.POINTER(f)], None),
+           "vd_run_device_punct_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, i, ctypes.c_uint32, ctypes.c_uint32, vp], None),
+           "vd_run_punct_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, i, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.POINTER(f)], None),
            "vd_kernel_name": ([i], ctypes.c_char_p),
            "vd_decoder_kernel_name": ([vp, sz, i, i], ctypes.c_char_p)}
     for name, (args, res) in sig.items():
@@ -263,7 +267,7 @@ class ViterbiCUDA:
         (vd_decoder_kernel_name: follows VD_NO_PK / VD_PK_SPLIT / VD_NO_SPLIT as read at creation); llr: False /
         0 packed input, True / 1 float channel values, 2 punctured float values, 3 a frame launch (inputNum =
         maxFrameBits, nbatch = nframes), 4 a launch of punctured frames (likewise), 5 a launch of tail-biting
-        frames (likewise)"""
+        frames (likewise), 6 a launch of punctured tail-biting frames (likewise; "-" on a HARD decoder)"""
         return lib().vd_decoder_kernel_name(self._h, inputNum, nbatch, int(llr)).decode()
 
     def set_guard_check(self, enable=True):
@@ -460,6 +464,45 @@ class ViterbiCUDA:
         _check(lib().vd_run_device_tb_frames(self._h, ctypes.c_void_p(llr_ptr), llr_stride, ctypes.c_void_p(output_ptr),
                                              output_stride, ctypes.c_void_p(frame_bits_ptr) if frame_bits_ptr else None,
                                              maxFrameBits, nframes, scale, ctypes.c_void_p(stream)))
+
+    # ---- punctured tail-biting frames: the kept float values of every frame, both index maps in the loads ----
+    def run_punct_tb_frames(self, rx_h, pattern, maxFrameBits, scale=40000.0, frame_bits=None):
+        """Blocking decode of nframes punctured tail-biting frames in one launch.  rx_h: float array [nframes, L], L >=
+        punctured_len(pattern, 2 * maxFrameBits): row f starts with puncture(frame f's values, pattern), the
+        pattern's phase at 0 at the frame's first stage and restarting at every wrap (the row pitch is the stride);
+        pattern = (period, keep0, keep1), e.g. PUNCTURE["3/4"]; frame_bits: the stages of each frame (not received
+        floats), as in run_frames.  Frame f equals, word for word, run_tb_frames of depuncture(its received values,
+        pattern, 2 S_f): the one-chunk decode of wrap_frame(depuncture(...)).  SOFT4, SOFT8, SOFT16 and FP32
+        decoders (HARD: VD_ERR_OPTIONS).  Returns (out, ms) shaped as run_tb_frames does."""
+        rx_h = np.ascontiguousarray(rx_h, dtype=np.float32)
+        if rx_h.ndim != 2:
+            raise VitdecError("run_punct_tb_frames: rx_h must be [nframes, L]")
+        need = punctured_len(pattern, 2 * maxFrameBits)  # (0 too for an invalid pattern, which the call below reports)
+        if rx_h.shape[1] < need:
+            raise VitdecError(f"run_punct_tb_frames: rows of {rx_h.shape[1]} received values, punctured_len{tuple(pattern)} "
+                              f"of {2 * maxFrameBits} is {need}")
+        nframes = rx_h.shape[0]
+        row = frame_output_size(self.options, maxFrameBits)
+        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
+        fb = None
+        if frame_bits is not None:
+            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
+            if fb.shape != (nframes,):
+                raise VitdecError("run_punct_tb_frames: frame_bits must hold one length per frame")
+        ms = ctypes.c_float(0.0)
+        _check(lib().vd_run_punct_tb_frames(self._h, rx_h.ctypes.data, 4 * rx_h.shape[1], out.ctypes.data, row,
+                                            fb.ctypes.data if fb is not None else None, maxFrameBits, nframes, scale,
+                                            *pattern, ctypes.byref(ms)))
+        return out, ms.value
+
+    def run_device_punct_tb_frames(self, rx_ptr, rx_stride, output_ptr, output_stride, maxFrameBits, nframes, pattern,
+                                   scale=40000.0, frame_bits_ptr=0, stream=0):
+        """Async decode of nframes punctured tail-biting frames in one launch (vd_run_device_punct_tb_frames):
+        pointers, strides and lengths as run_device_punct_frames; frame f reads exactly its punctured_len(pattern,
+        2 S_f) floats and writes 4 * ceil(S_f / 32) bytes."""
+        _check(lib().vd_run_device_punct_tb_frames(self._h, ctypes.c_void_p(rx_ptr), rx_stride, ctypes.c_void_p(output_ptr),
+                                                   output_stride, ctypes.c_void_p(frame_bits_ptr) if frame_bits_ptr else None,
+                                                   maxFrameBits, nframes, scale, *pattern, ctypes.c_void_p(stream)))
 
 
 class PinnedArray:

@@ -179,9 +179,10 @@ int vd_run_punct(vd_decoder* dec, const float* rx_h, void* output_h, size_t inpu
  * decodes one frame, and all frames go in one launch.  Every format and metric; an open frame needs a neutral
  * code, so a HARD decoder with terminated = 0 gets VD_ERR_OPTIONS.  VD_ERR_ARG: maxFrameBits outside
  * [1, 2^20], nframes < 1, scale not finite and > 0, a misaligned pointer or stride, overlapping frames.
- * Punctured frames: vd_run_device_punct_frames below; tail-biting frames: vd_run_device_tb_frames below.
- * Packed-word frames, frames longer than 2^20 stages, punctured tail-biting frames and vd_decode_pk twins of the
- * frame kernels are not supported. */
+ * Punctured frames: vd_run_device_punct_frames below; tail-biting frames: vd_run_device_tb_frames below; punctured
+ * tail-biting frames: vd_run_device_punct_tb_frames below.
+ * Packed-word frames, frames longer than 2^20 stages and vd_decode_pk twins of the frame kernels are not
+ * supported. */
 
 /* bytes a frame of frameBits stages decodes to: 4 * ceil(frameBits / 32), for O_B32 and O_B16 alike */
 size_t vd_frame_output_size(int options, size_t frameBits);
@@ -249,8 +250,7 @@ int vd_run_punct_frames(vd_decoder* dec, const float* rx_h, size_t rx_stride, vo
  * decodes the interior of any stream; no iterations, no search over start states.  No pad stages and no
  * erasures, so every format and metric is supported, HARD included.  The extended stream is never stored: the
  * wrap-around sits in the loads of the branch-metric table build, one wave decodes one frame, all frames go in
- * one launch.  Punctured tail-biting frames are not supported yet: until then a caller depunctures them into
- * 2 S floats (+0.0f at the punctured positions; not for HARD decoders). */
+ * one launch.  Punctured tail-biting frames: vd_run_device_punct_tb_frames below. */
 
 /* nframes tail-biting frames in one launch, under the rules of vd_run_device_frames (asynchronous, no allocation,
  * capturable, the stream on the decoder's device; the same pointers, strides and lengths array, no terminated
@@ -266,6 +266,41 @@ int vd_run_device_tb_frames(vd_decoder* dec, const float* llr_d, size_t llr_stri
  * no frame writes keep their values.  kernel_ms as in vd_run. */
 int vd_run_tb_frames(vd_decoder* dec, const float* llr_h, size_t llr_stride, void* output_h, size_t output_stride,
                      const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, float scale, float* kernel_ms);
+
+/* ---- punctured tail-biting frames (new: the two features above in one launch, e.g. 802.16 OFDMA's tail-biting
+ *      code at rates 2/3 and 3/4) ----
+ * A punctured tail-biting frame of S >= 1 stages under a pattern (period, keep0, keep1) -- the rules of
+ * vd_punctured_len -- is stored as the kept values of its 2 S mother-code values, in mother order, as floats:
+ * vd_punctured_len(period, keep0, keep1, 2 S) of them.  The pattern's phase belongs to the frame stage: frame stage
+ * t uses bit t % period.  Stage p of the extended stream is frame stage t = (p - 26) mod S and takes the phase of
+ * t, so the phase restarts at every wrap, also when S is not a multiple of period.  The decode equals, word for
+ * word, vd_run_device_tb_frames of the depunctured frame: 2 S floats, the received value at kept positions and
+ * +0.0f at punctured ones, same scale and options.  The pattern (1, 1, 1) gives exactly vd_run_device_tb_frames of
+ * the same buffer.  A frame too short to hold any kept value (e.g. (16, 0x8000, 0) with S <= 15) is legal: it reads
+ * nothing and decodes as the all-erasure frame.  Neither the depunctured frame nor the extended stream is ever
+ * stored: both index maps sit in the loads of the branch-metric table build.  SOFT4, SOFT8, SOFT16 and FP32
+ * decoders; a HARD decoder gets VD_ERR_OPTIONS (a punctured value has no hard code).  No pad value, so the scale
+ * only has to be finite and > 0.  One pass, no iterations.  The window limit of punctured streams carries over:
+ * rates above 3/4 decode exactly as defined but not error-free. */
+
+/* nframes punctured tail-biting frames in one launch, under the rules of vd_run_device_punct_frames without its
+ * terminated argument (asynchronous, no allocation, capturable, the stream on the decoder's device).  frame_bits_d
+ * and maxFrameBits count stages, not received floats: S_f = min(frame_bits_d[f], maxFrameBits), or maxFrameBits
+ * when frame_bits_d is NULL.  Frame f reads exactly vd_punctured_len(period, keep0, keep1, 2 S_f) floats at rx_d +
+ * f * rx_stride bytes and writes exactly vd_frame_output_size(S_f) bytes at output_d + f * output_stride bytes;
+ * S_f = 0 writes nothing.  rx_d, rx_stride and output_stride are multiples of 4.  VD_ERR_ARG: an invalid pattern,
+ * maxFrameBits outside [1, 2^20], nframes < 1, scale not finite and > 0, a misaligned pointer or stride, and with
+ * nframes > 1 rx_stride < 4 * vd_punctured_len(period, keep0, keep1, 2 * maxFrameBits) or output_stride <
+ * vd_frame_output_size(maxFrameBits). */
+int vd_run_device_punct_tb_frames(vd_decoder* dec, const float* rx_d, size_t rx_stride, void* output_d, size_t output_stride,
+                                  const uint32_t* frame_bits_d /* device, or NULL: every frame has maxFrameBits */,
+                                  size_t maxFrameBits, int nframes, float scale, int period, uint32_t keep0, uint32_t keep1,
+                                  void* stream);
+/* Blocking host-to-host variant over host buffers of the same layout (H2D, the launch, D2H); the output bytes
+ * no frame writes keep their values.  kernel_ms as in vd_run. */
+int vd_run_punct_tb_frames(vd_decoder* dec, const float* rx_h, size_t rx_stride, void* output_h, size_t output_stride,
+                           const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, float scale, int period,
+                           uint32_t keep0, uint32_t keep1, float* kernel_ms);
 
 /* ---- the reference harness's channel source (RandBitGen | ConvolutionalEncoder | AddNoise |
  *      SoftDecisionPacker, viterbiDF.h:20-167), host and GPU ---- */
@@ -320,7 +355,9 @@ const char* vd_kernel_name(int options);
  * decoder); llr 3: the frame launch of vd_run_device_frames (vd_decode_tg<FRM+...>), with inputNum =
  * maxFrameBits and nbatch = nframes; llr 4: the launch of vd_run_device_punct_frames (vd_decode_tg<FRM+PUN+...>),
  * inputNum and nbatch as for llr 3, "-" on a HARD decoder; llr 5: the launch of vd_run_device_tb_frames
- * (vd_decode_tg<FRM+TB+...>), inputNum and nbatch as for llr 3; valid until the thread's next call */
+ * (vd_decode_tg<FRM+TB+...>), inputNum and nbatch as for llr 3; llr 6: the launch of
+ * vd_run_device_punct_tb_frames (vd_decode_tg<FRM+TB+PUN+...>), inputNum and nbatch as for llr 3, "-" on a HARD
+ * decoder; valid until the thread's next call */
 const char* vd_decoder_kernel_name(vd_decoder* dec, size_t inputNum, int nbatch, int llr);
 /* build record: "<16 hex digits of the SHA-256 of the concatenated sources> <their paths, relative to the
  * package directory>"; the Python binding refuses a library whose sources have changed since (stale build) */
