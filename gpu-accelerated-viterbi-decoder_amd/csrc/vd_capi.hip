@@ -97,6 +97,7 @@ struct vd_decoder {
     DeviceState* ds = nullptr;  // the device's board / segment tables (looked up once, vd_create)
     Knobs knobs;                // VD_NO_SPLIT / VD_SPLIT / VD_NO_PK / VD_PK_SPLIT / VD_PK_TAIL as read at vd_create
     uint32_t* check = nullptr;  // LDS guard violation counter (vd_set_guard_check), null = off
+    uint32_t partBits = 0;      // frame launches decode frames in parts of this many stages (vd_set_frame_part_bits), 0 = whole
 };
 
 // a device buffer of at least need bytes (contents not kept)
@@ -264,7 +265,9 @@ const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, i
     if (llr == 6 && ch_of(d->options) == HARD) return "-";  // ... nor punctured tail-biting HARD frames
     if (llr == 3 || llr == 4 || llr == 5 || llr == 6) {  // a frame launch (4: of punctured, 5: of tail-biting, 6: of punctured tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
         if (inputNum < 1 || inputNum > kFrmMaxBits) return "-";
-        name = plan_name(plan_frames(d->options, (uint64_t)nbatch), d->options, llr);
+        if (frame_parts_error(inputNum, nbatch, d->partBits)) return "-";  // (more workgroups than a launch can have)
+        name = plan_name(plan_frames(d->options, (uint64_t)nbatch, frame_parts((uint32_t)inputNum, frame_part_words(d->partBits))),
+                         d->options, llr);
         return name.c_str();
     }
     name = plan_name(plan_of(d, inputNum, (uint32_t)nbatch, llr != 0, llr == 2), d->options, llr == 2 ? 2 : llr != 0);
@@ -556,6 +559,21 @@ size_t vd_frame_output_size(int options, size_t frameBits)
     return 4 * ((frameBits + 31) / 32);
 }
 
+// frames in parts (vd_frames.h "frames in parts"): the part length every frame entry point of the decoder reads
+int vd_set_frame_part_bits(vd_decoder* d, size_t partBits)
+{
+    if (!d) return fail(VD_ERR_ARG, "null argument");
+    if (!frame_part_bits_valid(partBits)) return fail(VD_ERR_ARG, "partBits must be 0 or a multiple of 96 in [96, 2^20]");
+    d->partBits = (uint32_t)partBits;
+    return VD_OK;
+}
+int vd_frame_part_bits(vd_decoder* d, size_t* partBits)
+{
+    if (!d || !partBits) return fail(VD_ERR_ARG, "null argument");
+    *partBits = d->partBits;
+    return VD_OK;
+}
+
 // the argument checks of a frame decode: VD_ERR_ARG / VD_ERR_OPTIONS
 static int frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, const void* output, size_t output_stride,
                        size_t maxFrameBits, int nframes, int terminated, float scale, bool device)
@@ -564,6 +582,7 @@ static int frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, 
     if (const char* why = frame_args_error(device ? (uint64_t)(uintptr_t)llr : 0, llr_stride, output_stride, maxFrameBits,
                                            nframes, scale))
         return fail(VD_ERR_ARG, why);
+    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
     if (ch_of(d->options) == HARD && !terminated)
         return fail(VD_ERR_OPTIONS, "open frames on a HARD decoder: the stages after an open frame are erasures, and HARD's "
                                     "v > 0 ? 1 : 0 has no neutral code; terminate the frames or use SOFT4, SOFT8, SOFT16 or FP32");
@@ -577,7 +596,10 @@ static int launch_frames_checked(vd_decoder* d, const float* llr_d, size_t llr_s
                                  hipStream_t s, const Punct* pun = nullptr, bool tb = false)
 {
     const int options = d->options;
-    const LaunchPlan p = plan_frames(options, (uint64_t)nframes);
+    // the decoder's part length, read here, on the host: a captured graph keeps the value it was captured with
+    const uint32_t partBits = d->partBits;
+    if (const char* why = frame_parts_error(maxFrameBits, nframes, partBits)) return fail(VD_ERR_ARG, why);
+    const LaunchPlan p = plan_frames(options, (uint64_t)nframes, frame_parts((uint32_t)maxFrameBits, frame_part_words(partBits)));
     launch_fn f = tb && pun ? launcher_punct_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                   : tb  ? launcher_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                   : pun ? launcher_punct_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
@@ -604,6 +626,10 @@ static int launch_frames_checked(vd_decoder* d, const float* llr_d, size_t llr_s
     g.frmTerm = terminated ? 1u : 0u;
     if (!tb) frame_pad(scale, &g.frmPad);  // (checked by the caller)
     if (pun) g.pun = *pun;
+    if (p.parts > 1) {  // (one part: the grid and the arguments of a whole-frame launch)
+        g.frmPartW = frame_part_words(partBits);
+        g.frmPartG = frame_part_groups(p.parts);
+    }
     f(llr_d, output_d, g, p.grid, s);
     VD_HIP(hipGetLastError());
     return VD_OK;
@@ -671,6 +697,7 @@ static int punct_frames_args(const vd_decoder* d, const void* rx, size_t rx_stri
     if (const char* why = pfrm_args_error(device ? (uint64_t)(uintptr_t)rx : 0, rx_stride, output_stride, maxFrameBits, nframes,
                                           scale, period, keep0, keep1))
         return fail(VD_ERR_ARG, why);
+    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
     if (ch_of(d->options) == HARD)
         return fail(VD_ERR_OPTIONS, "punctured frames on a HARD decoder: a punctured value must decode as code 0 = value 0, "
                                     "and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");
@@ -733,6 +760,7 @@ static int tb_frames_args(const vd_decoder* d, const void* llr, size_t llr_strid
     if (const char* why = tb_args_error(device ? (uint64_t)(uintptr_t)llr : 0, llr_stride, output_stride, maxFrameBits, nframes,
                                         scale))
         return fail(VD_ERR_ARG, why);
+    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
     return VD_OK;
 }
 
@@ -785,6 +813,7 @@ static int punct_tb_frames_args(const vd_decoder* d, const void* rx, size_t rx_s
     if (const char* why = ptb_args_error(device ? (uint64_t)(uintptr_t)rx : 0, rx_stride, output_stride, maxFrameBits, nframes,
                                          scale, period, keep0, keep1))
         return fail(VD_ERR_ARG, why);
+    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
     if (ch_of(d->options) == HARD)
         return fail(VD_ERR_OPTIONS, "punctured tail-biting frames on a HARD decoder: a punctured value must decode as code 0 = "
                                     "value 0, and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");

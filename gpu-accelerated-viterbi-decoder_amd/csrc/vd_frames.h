@@ -199,7 +199,9 @@ VD_FRAMES_HD uint32_t tb_mod(uint32_t x, uint32_t S, uint32_t m32)
 }
 // some lane of the 96-stage group from extended stage g0 (a multiple of kFrmGroup) wraps: wave-uniform
 VD_FRAMES_HD bool tb_wrap_group(uint32_t g0, uint32_t S) { return g0 < kFrmLead || g0 + kFrmGroup - kFrmLead > S; }
-// frame stage of the group's lane 0: (g0 - 26) mod S, non-negative (g0 <= kFrmMaxBits + a few groups)
+// frame stage of the group's lane 0: (g0 - 26) mod S, non-negative (g0 <= kFrmMaxBits + a few groups; for the
+// groups of a part too, "frames in parts" below: a part starts below 32 W <= S + 31 and runs its own words + 2 blocks
+// and one prefetched group, so g0 - 26 < S + 32 (Wp + 2) + 96 < 2^21 + 2^20 + 200, far inside tb_mod's x < 2^31)
 VD_FRAMES_HD uint32_t tb_group_r0(uint32_t g0, uint32_t S, uint32_t m32)
 {
     if (g0 >= kFrmLead) return tb_mod(g0 - kFrmLead, S, m32);
@@ -329,6 +331,79 @@ inline const char* ptb_args_error(uint64_t rx_addr, uint64_t rx_stride, uint64_t
         return "rx_stride smaller than 4 * vd_punctured_len(2 * maxFrameBits): frames would overlap";
     if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
         return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
+    return nullptr;
+}
+
+// ---------------------------------------------------------------- frames in parts (all four families)
+// A decoder's part length partBits is 0 (whole frames: one frame per wave, everything above) or a multiple of 96
+// in [96, 2^20].  With Wp = partBits / 32 words (a multiple of 3) a frame of S stages, W = frame_words(S), has
+// ceil(W / Wp) parts; part j holds the w_j = min(Wp, W - j Wp) words from word j Wp on and is decoded by a wave
+// of its own as the one-chunk decode of stages [32 j Wp, 32 j Wp + 64 + 32 w_j) of the frame's padded or extended
+// stream: from equal metrics, 26 warm-up stages before its first bit and 38 traceback stages after its last, which
+// are the frame's own stages where it has them and pad stages, erasures or the wrap otherwise, by the per-stage
+// rules above.  32 j Wp is a multiple of 96, so every group of every part starts at a multiple of kFrmGroup of the
+// stream, as the groups of a whole frame do: the helpers above take such a first stage g0 unchanged (g0 <=
+// kFrmMaxBits + a few groups still holds: a part starts below 32 W).  A frame with W <= Wp is one part, the whole
+// frame.  Launch geometry: partsMax = ceil(frame_words(maxFrameBits) / Wp) parts at most, G = ceil(partsMax /
+// kFrmWaves) workgroups per frame, so the parts of a frame sit in neighbouring waves; wave wv of workgroup b is
+// part (b % G) kFrmWaves + wv of frame b / G, and a wave whose part starts at or past its frame's W has nothing
+// to do.  tests/cxx/frame_parts_check.cpp checks the helpers below against a plain enumeration.
+constexpr uint32_t kFrmWaves = 4;                    // waves per workgroup (kWaves, vd_kernels.h)
+constexpr uint32_t kFrmMaxGrid = 0x7FFFFFFFu;        // workgroups a launch may have
+
+// partBits is 0 or a multiple of 96 in [96, 2^20]
+VD_FRAMES_HD bool frame_part_bits_valid(uint64_t partBits)
+{
+    return partBits == 0 || (partBits >= kFrmGroup && partBits <= kFrmMaxBits && partBits % kFrmGroup == 0);
+}
+// Wp: the 32-bit words of a part (0: whole frames)
+VD_FRAMES_HD uint32_t frame_part_words(uint32_t partBits) { return partBits / 32u; }
+// the parts of a frame of S stages: ceil(W / Wp); 1 for whole frames (Wp = 0)
+VD_FRAMES_HD uint32_t frame_parts(uint32_t S, uint32_t Wp)
+{
+    const uint32_t W = frame_words(S);
+    return Wp == 0 || W <= Wp ? 1u : (W + Wp - 1u) / Wp;
+}
+// part j of a frame of S stages: its first word and its words (0: the part starts at or past the frame's W)
+struct FramePart {
+    uint32_t word0, words;
+};
+VD_FRAMES_HD FramePart frame_part(uint32_t S, uint32_t Wp, uint32_t j)
+{
+    const uint32_t W = frame_words(S);
+    if (Wp == 0) return {0u, j == 0 ? W : 0u};
+    const uint32_t w0 = j * Wp;  // j <= partsMax + kFrmWaves, Wp <= 2^15: below 2^32
+    if (w0 >= W) return {w0, 0u};
+    return {w0, W - w0 < Wp ? W - w0 : Wp};
+}
+// first stage of part j in the frame's padded or extended stream: a multiple of kFrmGroup
+VD_FRAMES_HD uint32_t frame_part_stage(uint32_t Wp, uint32_t j) { return 32u * j * Wp; }
+// workgroups per frame of a launch whose longest frame has partsMax parts
+VD_FRAMES_HD uint32_t frame_part_groups(uint32_t partsMax) { return (partsMax + kFrmWaves - 1u) / kFrmWaves; }
+// the frame and part of wave wv (< kFrmWaves) of workgroup b at G workgroups per frame
+struct FrameWave {
+    uint32_t frame, part;
+};
+VD_FRAMES_HD FrameWave frame_wave(uint32_t b, uint32_t wv, uint32_t G)
+{
+    const uint32_t f = b / G;
+    return {f, (b - f * G) * kFrmWaves + wv};
+}
+// the workgroups of a launch of nframes frames of at most maxFrameBits stages in parts of partBits (64 bits: the
+// caller compares with kFrmMaxGrid)
+inline uint64_t frame_parts_grid(uint64_t nframes, uint32_t maxFrameBits, uint32_t partBits)
+{
+    const uint32_t parts = frame_parts(maxFrameBits, frame_part_words(partBits));
+    if (parts <= 1) return (nframes + kFrmWaves - 1u) / kFrmWaves;
+    return nframes * frame_part_groups(parts);
+}
+// the argument check a part length adds to every frame entry point (VD_ERR_ARG): the message, or null
+inline const char* frame_parts_error(uint64_t maxFrameBits, int nframes, uint64_t partBits)
+{
+    if (!frame_part_bits_valid(partBits)) return "partBits must be 0 or a multiple of 96 in [96, 2^20]";
+    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits || nframes < 1) return nullptr;  // (the family's own check reports these)
+    if (frame_parts_grid((uint64_t)nframes, (uint32_t)maxFrameBits, (uint32_t)partBits) > kFrmMaxGrid)
+        return "nframes frames in parts of partBits need more than 2^31 - 1 workgroups";
     return nullptr;
 }
 

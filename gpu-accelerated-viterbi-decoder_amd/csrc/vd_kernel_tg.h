@@ -673,6 +673,11 @@ __device__ __forceinline__ float2 tg_pun_load(__amdgpu_buffer_rsrc_t rs, const P
 // branch that only groups touching a pad stage take (the first, and for terminated frames the ones from the
 // frame's end on): no flag waits in a VGPR for a group, and the prefetch is not waited on early.
 // Everything after the loads is TgInLlr<BASE>: the same quantisation, table rows, cores, ring and traceback.
+// Frames in parts (Geom::frmPartW = Wp > 0; vd_frames.h "frames in parts", all four families): wave wv of workgroup
+// b decodes part (b % G) kWaves + wv of frame b / G, the words [j Wp, j Wp + w_j) of the frame, as a chunk whose
+// first stage is stage 32 j Wp of the same padded or extended stream.  That stage (the run's `start`, wave-uniform,
+// a multiple of 96) is added to the stage of the group-0 loads, of the per-group loads and of the pad predicate;
+// resource, range and per-stage rules are the frame's.  With Wp = 0 the start is 0 and the launch is the above.
 template <int BASE>
 struct TgInFrm : TgInLlr<BASE> {
     static constexpr bool FRM = true;
@@ -699,8 +704,9 @@ __device__ __forceinline__ float2 tg_frm_load(__amdgpu_buffer_rsrc_t rs, uint32_
 // stream: one resource per frame over its received bytes (pfrm_bytes, once per wave on the scalar unit), per
 // group the scalar (4 q0 Kp, r0) of its first frame stage (pfrm_group, pfrm_base), per lane two single-dword
 // loads at the vector offsets of pfrm_offsets.  Punctured values, lead stages and every stage from the frame's
-// end on read zero through the range check: no flag waits in a VGPR.  The first loads of a wave are group 0's
-// (lead 26, frame stage 0: q0 = r0 = 0), every later group has no lead stage, so both forms fold at compile time.
+// end on read zero through the range check: no flag waits in a VGPR.  The first loads of a wave are the frame's
+// group 0 (lead 26, frame stage 0: q0 = r0 = 0) or a later part's first group (no lead), told apart by scalar
+// values once per wave; every group after the first has no lead stage, which folds at compile time.
 template <int BASE>
 struct TgInPfr : TgInLlr<BASE> {
     static_assert(BASE != HARD, "HARD has no neutral code for an erasure");
@@ -912,29 +918,44 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     // This wave's work: chunk blockIdx.x * kWaves + wv, or, in a segment launch (Geom::seg), segment wv of
     // the workgroup's chunks -- see "segment launches" above.
     // A batched launch (Geom::nbatch > 1) decodes chunk c of batch b at launch chunk b * nchunks + c.
-    // (a frame is never split: the punctured-frame, tail-biting and punctured tail-biting kernels are compiled
-    // without the segment machinery, which otherwise costs the punctured SOFT8 / M_B16 one a spilled VGPR)
-    const bool split = HasPfr<IN>::value || HasTbf<IN>::value || HasPtb<IN>::value ? false : geo.seg != nullptr;
+    // (a frame launch has no segment table -- a long frame goes in parts, below -- so the frame kernels are compiled
+    // without the segment machinery: its scalars, spilled to VGPR lanes at 8 waves per SIMD, otherwise push the
+    // frame kernels into scratch)
+    const bool split = HasFrm<IN>::value ? false : geo.seg != nullptr;
     const int piece = split ? wv : -1;
     const uint32_t gchunk = blockIdx.x * kWaves + wv;
-    constexpr bool FRM = HasFrm<IN>::value;  // frame launch: this wave decodes frame gchunk whole (never split)
-    uint32_t frmS = 0;                       // its stages (wave-uniform)
+    // frame launch: this wave decodes frame gchunk whole, or (Geom::frmPartW, vd_frames.h "frames in parts") one
+    // part of frame blockIdx.x / G: the words [frmW0, frmW0 + frmWn) of the frame, as a chunk of their own
+    constexpr bool FRM = HasFrm<IN>::value;
+    uint32_t frmS = 0;                       // the frame's stages (wave-uniform, as everything here)
+    uint32_t frmF = gchunk;                  // the frame
+    uint32_t frmW0 = 0, frmWn = 0;           // this wave's 32-bit words of it: the first, the count
     if constexpr (FRM) {
-        if (gchunk >= geo.nbatch) return;  // the last workgroup's waves past the last frame
-        const uint32_t n = geo.frmBits ? geo.frmBits[gchunk] : geo.frmMax;
+        uint32_t part = 0;
+        if (geo.frmPartW) {  // the one division of the wave's set-up (uniform operands)
+            const FrameWave fw = frame_wave(blockIdx.x, (uint32_t)wv, geo.frmPartG);
+            frmF = __builtin_amdgcn_readfirstlane(fw.frame);
+            part = __builtin_amdgcn_readfirstlane(fw.part);
+        }
+        if (frmF >= geo.nbatch) return;  // the last workgroup's waves past the last frame
+        const uint32_t n = geo.frmBits ? geo.frmBits[frmF] : geo.frmMax;
         frmS = __builtin_amdgcn_readfirstlane(n < geo.frmMax ? n : geo.frmMax);
+        const FramePart fp = frame_part(frmS, geo.frmPartW, part);  // no words: the wave returns below, before any load
+        frmW0 = __builtin_amdgcn_readfirstlane(fp.word0);
+        frmWn = __builtin_amdgcn_readfirstlane(fp.words);
     }
     constexpr bool TBF = HasTbf<IN>::value;  // ... a tail-biting frame: wrapped loads, no pad (tg_tbf_load)
     constexpr bool PFR = HasPfr<IN>::value;  // ... of the kept values of a punctured frame (tg_pfr_load)
     constexpr bool PTB = HasPtb<IN>::value;  // ... of a punctured tail-biting frame: both maps (tg_ptb_load)
     uint32_t pfrB = 0;                       // its received bytes (wave-uniform)
     if constexpr (PFR || PTB) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes(geo.pun, frmS));
-    const uint32_t batch = FRM ? gchunk : geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
+    const uint32_t batch = FRM ? frmF : geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
     const void* const in = (const char*)in_all + batch * geo.inStride;
     void* const out = (char*)out_all + batch * geo.outStride;
-    // a chunk's first output word and its words (a frame: the chunk of its own one-chunk decode)
+    // a chunk's first output word and its words (a frame or a part of one: the chunk of its own one-chunk decode,
+    // whose first stage, 32 frmW0, the run's `start` below carries into the loads and the pad predicate)
     auto crange = [&](uint32_t c) {
-        if constexpr (FRM) return ChunkRange{0, frame_words(frmS) * (OB == 32 ? 1u : 2u)};
+        if constexpr (FRM) return ChunkRange{frmW0 * (OB == 32 ? 1u : 2u), frmWn * (OB == 32 ? 1u : 2u)};
         else return chunk_range(geo, c);
     };
     auto words32 = [&](uint32_t c) {  // 32-bit words traced back in chunk c
@@ -1003,8 +1024,12 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     // In a batched launch only the last batch's waves run the controller: earlier batches' waves are
     // followed by more work on their SIMD, so evening out progress buys nothing there and costs issue
     // (1.6 % per batch, profiles/r02/benchab_fair2.log).
-    // (a frame launch: the waves of its last kChunks frames, as the last batch of a batched launch)
-    fair.begin((FRM ? batch + kChunks < geo.nbatch : batch + 1 < geo.nbatch) ? nullptr : geo.fair, lane);
+    // (a frame launch: the waves of its last kChunks frames, as the last batch of a batched launch; in parts: the
+    // launch's last kChunks waves, the last kChunks / kWaves of its nbatch G workgroups)
+    bool fairOff = batch + 1 < geo.nbatch;
+    if constexpr (FRM)
+        fairOff = geo.frmPartW ? geo.nbatch * geo.frmPartG - blockIdx.x > (uint32_t)(kChunks / kWaves) : batch + kChunks < geo.nbatch;
+    fair.begin(fairOff ? nullptr : geo.fair, lane);
     // fairness progress: blocks started, or in a segment launch the fraction of the segment's pass-0
     // blocks started, scaled to 2^20 (its waves differ in length)
     uint32_t fscale = 1u;
@@ -1047,27 +1072,35 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     uint32_t tbn = pass == 0 ? LL::TBS - 3 * (blockIdx.x & 3) : LL::TBS;
     __amdgpu_buffer_rsrc_t rs;
     typename IN::raw_t rA, rB;  // the input of stages sA and sB of the group
-    if constexpr (PFR) {  // one resource for the whole frame: its received bytes; group 0 (start = 0, j0 = 0)
+    // a frame run's first stage in the frame's padded or extended stream: 0, or 32 frmW0 of a later part, a multiple
+    // of kFrmGroup <= kFrmMaxBits (j0 = 0: a frame is never re-decoded); every group of the run starts at fst + 32 j
+    const uint32_t fst = FRM ? __builtin_amdgcn_readfirstlane((uint32_t)start) : 0u;
+    if constexpr (PFR) {  // one resource for the whole frame: its received bytes
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)pfrB, 0x00020000);
-        constexpr PfrmGroup pg = pfrm_group(0u);
-        static_assert(pg.t0 == 0, "group 0 starts at frame stage 0: q0 = r0 = 0");
-        rA = tg_pfr_load(rs, geo.pun, 0u, 0u, pg.lead, (uint32_t)sA);
-        rB = tg_pfr_load(rs, geo.pun, 0u, 0u, pg.lead, (uint32_t)sB);
-    } else if constexpr (PTB) {  // one resource for the whole frame: its received bytes; group 0 wraps its lead
+        // the run's group 0: the frame's (fst = 0: 26 lead stages, then frame stage 0, for which pfrm_base gives
+        // q0 = r0 = 0), or a later part's (no lead stage, frame stage fst - 26)
+        const PfrmGroup pg = pfrm_group(fst);
+        uint32_t r0;
+        const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
+        r0 = __builtin_amdgcn_readfirstlane(r0);
+        const uint32_t lead = __builtin_amdgcn_readfirstlane(pg.lead);
+        rA = tg_pfr_load(rs, geo.pun, base4, r0, lead, (uint32_t)sA);
+        rB = tg_pfr_load(rs, geo.pun, base4, r0, lead, (uint32_t)sB);
+    } else if constexpr (PTB) {  // one resource for the whole frame: its received bytes; the frame's group 0 wraps its lead
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)pfrB, 0x00020000);
-        tg_ptb_load(rs, geo.pun, 0u, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+        tg_ptb_load(rs, geo.pun, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
     } else if constexpr (PUN) {
         uint32_t r0;
         rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
         rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
         rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
-    } else if constexpr (TBF) {  // one resource for the whole frame: its 8 frmS bytes; group 0 wraps its lead
+    } else if constexpr (TBF) {  // one resource for the whole frame: its 8 frmS bytes; the frame's group 0 wraps its lead
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(8u * frmS), 0x00020000);
-        tg_tbf_load(rs, 0u, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
-    } else if constexpr (FRM) {  // one resource for the whole frame: its 8 frmS bytes (start = 0, j0 = 0)
+        tg_tbf_load(rs, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+    } else if constexpr (FRM) {  // one resource for the whole frame: its 8 frmS bytes
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(8u * frmS), 0x00020000);
-        rA = tg_frm_load(rs, (uint32_t)sA);
-        rB = tg_frm_load(rs, (uint32_t)sB);
+        rA = tg_frm_load(rs, fst + (uint32_t)sA);
+        rB = tg_frm_load(rs, fst + (uint32_t)sB);
     } else {
         rs = tg_rsrc<CH>(in, start + 32ull * j0, availB);
         rA = IN::template load<0>(rs, vo1);
@@ -1228,7 +1261,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         if constexpr (FRM && !TBF && !PTB) {
             // the pad value in the lanes of this group's pad stages (vd_frames.h): a uniform branch that the
             // groups inside the frame skip
-            const uint32_t g0 = 32u * j, end = frame_end(frmS, geo.frmTerm != 0);
+            const uint32_t g0 = fst + 32u * j, end = frame_end(frmS, geo.frmTerm != 0);
             if (frame_pad_group(g0, end)) {
                 const float2 pad = make_float2(geo.frmPad, geo.frmPad);
                 if (frame_pad_stage(g0 + (uint32_t)sA, end)) rA = pad;
@@ -1258,7 +1291,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             }
         }
         if constexpr (PFR) {  // the next group's kept values: (4 q0 Kp, r0) of its first frame stage, scalar unit
-            const uint32_t g0n = 32u * (j + 3);
+            const uint32_t g0n = fst + 32u * (j + 3);
             __builtin_assume(g0n >= kFrmGroup);  // (no lead stage: pg.lead folds to 0)
             const PfrmGroup pg = pfrm_group(g0n);
             uint32_t r0;
@@ -1267,7 +1300,7 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             rA = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sA);
             rB = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sB);
         } else if constexpr (PTB) {  // the next group's kept values of the extended stream: the frame, wrapped
-            const uint32_t g0n = 32u * (j + 3);
+            const uint32_t g0n = fst + 32u * (j + 3);
             __builtin_assume(g0n >= kFrmGroup);  // (no lead: tb_wrap_group and tb_group_r0 fold to their g0 >= 26 forms)
             tg_ptb_load(rs, geo.pun, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
         } else if constexpr (PUN) {  // the next group's received values, at the offsets of its own r0
@@ -1276,12 +1309,12 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
             rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
         } else if constexpr (TBF) {  // the next group's stages of the extended stream: the frame, wrapped
-            const uint32_t g0n = 32u * (j + 3);
+            const uint32_t g0n = fst + 32u * (j + 3);
             __builtin_assume(g0n >= kFrmGroup);  // (no lead: tb_wrap_group and tb_group_r0 fold to their g0 >= 26 forms)
             tg_tbf_load(rs, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
         } else if constexpr (FRM) {  // the next group's stages of the padded stream
-            rA = tg_frm_load(rs, 32u * (j + 3) + (uint32_t)sA);
-            rB = tg_frm_load(rs, 32u * (j + 3) + (uint32_t)sB);
+            rA = tg_frm_load(rs, fst + 32u * (j + 3) + (uint32_t)sA);
+            rB = tg_frm_load(rs, fst + 32u * (j + 3) + (uint32_t)sB);
         } else
         {  // the next group's input words
             rs = tg_rsrc<CH>(in, start + 32ull * (j + 3), availB);

@@ -75,6 +75,10 @@ struct Geom {
     uint32_t frmMax = 0;
     uint32_t frmTerm = 0;
     float frmPad = 0.0f;
+    // frames in parts (vd_frames.h "frames in parts"): frmPartW = Wp, the 32-bit words of a part, 0 = one frame per
+    // wave; frmPartG = the workgroups per frame (wave wv of workgroup b: part (b % G) kWaves + wv of frame b / G)
+    uint32_t frmPartW = 0;
+    uint32_t frmPartG = 1;
 };
 // Progress board of the fairness controller: per SIMD slot (XCC, SE, SH, CU, SIMD from the hardware
 // wave id) kFairWaves 32-bit words, one per hardware wave slot of that SIMD (HW_ID.WAVE_ID): the blocks
@@ -133,6 +137,7 @@ __host__ __device__ __forceinline__ ChunkRange chunk_range(const Geom& g, uint32
 // barriers (wg_sync_lds(), vd_kernel_pk.h "Batched"; every wave of the workgroup runs the same number of
 // blocks and passes, vd_pk_wg.h).
 constexpr int kWaves = 4;
+static_assert(kWaves == (int)kFrmWaves, "vd_frames.h maps the parts of a frame to the waves of a workgroup");
 __device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -255,6 +255,7 @@ struct LaunchPlan {
     int seg = kSegNone;     // the SegMode of a segment launch's table (Geom::seg)
     bool stats = false;     // Geom::stats set: segment and split launches count their re-decodes
     uint64_t packNum = 0;   // Geom::packNum
+    uint32_t parts = 1;     // frame launches: the parts of the longest frame (1: one frame per wave)
 };
 
 // nbatch batches of inputNum encoded values on a device of nsimd SIMDs whose segment tables (vd_segplan.h,
@@ -302,13 +303,17 @@ inline LaunchPlan plan_launch(int o, size_t inputNum, uint32_t nbatch, bool llr,
 }
 
 // nframes independent frames (vd_frames.h): one frame per wave on vd_decode_tg<FRM+...>, whatever the knobs say
-// (no vd_decode_pk twins, no segment launch: a frame is never split)
-inline LaunchPlan plan_frames(int o, uint64_t nframes)
+// (no vd_decode_pk twins, no segment launch)
+// partsMax > 1 (vd_frames.h "frames in parts"): the launch's longest frame has that many parts, every frame gets
+// G = frame_part_groups(partsMax) workgroups and each of their waves one part; the caller has checked
+// frame_parts_error, so nframes G fits the grid
+inline LaunchPlan plan_frames(int o, uint64_t nframes, uint32_t partsMax = 1)
 {
     LaunchPlan p;
     p.launches = valid(o) && nframes != 0;
     p.form = Form::Tg;
-    p.grid = (unsigned)((nframes + kWaves - 1) / kWaves);
+    p.parts = partsMax > 1 ? partsMax : 1u;
+    p.grid = p.parts > 1 ? (unsigned)(nframes * frame_part_groups(p.parts)) : (unsigned)((nframes + kWaves - 1) / kWaves);
     return p;
 }
 
@@ -327,7 +332,8 @@ inline std::string plan_name(const LaunchPlan& p, int o, int input)
                                          input == 3 ? "FRM+" : input == 2 ? "PUN+" : input ? "LLR+" : "") +
                              kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," + (out_of(o) ? "O16" : "O32") + ">";
     if (input == 3 || input == 4 || input == 5 || input == 6)
-        return "vd_decode_tg<" + args + " one frame per wave, " + (ch_of(o) == SOFT16 ? "int32 tagged patterns" : "fp32 tagged core");
+        return "vd_decode_tg<" + args + " one frame per wave, " + (ch_of(o) == SOFT16 ? "int32 tagged patterns" : "fp32 tagged core") +
+               (p.parts > 1 ? ", " + std::to_string(p.parts) + " parts per frame: one part per wave" : "");
     if (p.form == Form::PkBatched) return "vd_decode_pk<" + args + " batched: two chunks per wave, int16 halves";
     if (p.form == Form::PkSplit) return "vd_decode_pk<" + args + " split: one chunk per wave cut in two, int16 halves";
     return "vd_decode_tg<" + args + (p.seg != kSegNone ? " segment launch: one chunk or piece per wave, " : " one chunk per wave, ") +

@@ -49,7 +49,7 @@ EXPORTS = ["vd_options_valid", "vd_input_size", "vd_message_len", "vd_output_siz
            "vd_decoder_kernel_name", "vd_punctured_len", "vd_run_device_punct", "vd_run_device_punct_batch",
            "vd_run_punct", "vd_frame_output_size", "vd_run_device_frames", "vd_run_frames",
            "vd_run_device_punct_frames", "vd_run_punct_frames", "vd_run_device_tb_frames", "vd_run_tb_frames",
-           "vd_run_device_punct_tb_frames", "vd_run_punct_tb_frames"]
+           "vd_run_device_punct_tb_frames", "vd_run_punct_tb_frames", "vd_set_frame_part_bits", "vd_frame_part_bits"]
 
 # puncture patterns (period, keep0, keep1): bit i of keep0 / keep1 = the first (0171) / second (0133) encoder
 # output of the stages t with t % period == i is transmitted.  Any valid masks decode (and equal the rate-1/2
@@ -118,6 +118,7 @@ def lib():
            "vd_run_device_punct_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, i, ctypes.c_uint32, ctypes.c_uint32, vp], None),
            "vd_run_punct_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, i, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.POINTER(f)], None),
+           "vd_set_frame_part_bits": ([vp, sz], None), "vd_frame_part_bits": ([vp, ctypes.POINTER(sz)], None),
            "vd_kernel_name": ([i], ctypes.c_char_p),
            "vd_decoder_kernel_name": ([vp, sz, i, i], ctypes.c_char_p)}
     for name, (args, res) in sig.items():
@@ -354,6 +355,19 @@ class ViterbiCUDA:
         output_stride bytes (strides multiples of 4 bytes; vd_run_device_punct_batch)."""
         _check(lib().vd_run_device_punct_batch(self._h, ctypes.c_void_p(rx_ptr), rx_stride, ctypes.c_void_p(output_ptr),
                                                output_stride, inputNum, scale, *pattern, nbatch, ctypes.c_void_p(stream)))
+
+    # ---- long frames in parts spread over many waves (vd_capi.h "long frames in parts") ----
+    def set_frame_part_bits(self, part_bits):
+        """Every frame entry point of this decoder decodes frames in parts of part_bits stages, one wave per part:
+        0 (the default) whole frames, else a multiple of 96 in [96, 2^20].  Part j of a frame equals, word for word,
+        the one-chunk decode of sub-stream j of frame_parts(the frame's padded or extended stream, part_bits).  Read
+        on the host at each call; not to be called while launches of this decoder are being issued."""
+        _check(lib().vd_set_frame_part_bits(self._h, part_bits))
+
+    def frame_part_bits(self):
+        v = ctypes.c_size_t(0)
+        _check(lib().vd_frame_part_bits(self._h, ctypes.byref(v)))
+        return v.value
 
     # ---- independent frames, decoded from first bit to last (vd_capi.h "independent frames") ----
     def run_frames(self, llr_h, terminated=True, scale=40000.0, frame_bits=None):
@@ -609,6 +623,28 @@ def wrap_frame(values):
     S = v.size // 2
     P = 64 + 32 * ((S + 31) // 32)
     return v.reshape(S, 2)[(np.arange(P) - FRAME_LEAD) % S].reshape(-1).copy()
+
+
+def frame_parts(stream, part_bits):
+    """The sub-streams that define a frame decode in parts (host helper; the contract the tests feed to the oracle).
+
+    stream: the 2 P floats, P = 64 + 32 W, of a frame's padded stream (pad_frame) or extended stream (wrap_frame);
+    part_bits: 0 (whole frames) or a multiple of 96 in [96, 2^20].  Yields (word0, words, sub) for part j = 0, 1,
+    ...: with Wp = part_bits / 32, word0 = j Wp, words = w_j = min(Wp, W - j Wp), and sub the 2 (64 + 32 w_j)
+    floats of stages [32 j Wp, 32 j Wp + 64 + 32 w_j) of the stream.  Part j of the frame decode equals the
+    one-chunk decode (nchunks = 1, inputNum = sub.size) of sub's SoftDecisionPacker packing, written at word word0
+    of the frame's output (O_B16: 16-bit words 2 word0 .. 2 word0 + 2 w_j - 1).  part_bits = 0, or >= 32 W, yields
+    the stream itself."""
+    v = np.ascontiguousarray(stream, dtype=np.float32).reshape(-1)
+    if v.size % 64 or v.size < 2 * 96:
+        raise VitdecError("frame_parts: a stream of 2 (64 + 32 W) floats, W >= 1")
+    if part_bits != 0 and (part_bits % 96 or not 96 <= part_bits <= 1 << 20):
+        raise VitdecError("frame_parts: part_bits must be 0 or a multiple of 96 in [96, 2^20]")
+    W = v.size // 64 - 2
+    Wp = part_bits // 32 if part_bits else W
+    for w0 in range(0, W, Wp):
+        w = min(Wp, W - w0)
+        yield w0, w, v[64 * w0:64 * w0 + 2 * (64 + 32 * w)]
 
 
 def simulate_host(options, n_bits, snr, bit_seed, noise_seed):

@@ -302,6 +302,30 @@ int vd_run_punct_tb_frames(vd_decoder* dec, const float* rx_h, size_t rx_stride,
                            const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, float scale, int period,
                            uint32_t keep0, uint32_t keep1, float* kernel_ms);
 
+/* ---- long frames in parts spread over many waves (new: a few long frames, e.g. one DVB or CCSDS burst, would
+ *      otherwise occupy a few waves of a GPU that holds thousands) ----
+ * A decoder carries a part length partBits: 0 (the default: one wave decodes a whole frame, everything above) or
+ * a multiple of 96 in [96, 2^20].  All eight frame entry points above honour it; their signatures and argument
+ * rules do not change.  With Wp = partBits / 32, a frame of S stages, W = ceil(S / 32), has ceil(W / Wp) parts,
+ * and part j holds w_j = min(Wp, W - j Wp) words.  Part j decodes, word for word, as the one-chunk decode
+ * (inputNum = 2 (64 + 32 w_j), nchunks = 1, O_B16 policy 0) of stages [32 j Wp, 32 j Wp + 64 + 32 w_j) of the
+ * frame's padded stream (frames, punctured frames) or extended stream (tail-biting, punctured tail-biting), and
+ * writes those w_j words (O_B16: 2 w_j) at word j Wp of the frame's output.  A frame with W <= Wp is one part and
+ * decodes exactly as with partBits = 0.  Each part is decoded by a wave of its own from equal metrics, with 26
+ * warm-up stages before it and 38 traceback stages after it: the frame's own stages where it has them, else pad
+ * stages, erasures or the wrap by the same per-stage rule as above.  This is the window every stream entry point
+ * uses at every chunk boundary; on noisy input a decode in parts can differ from the whole-frame decode in a few
+ * words, as two chunkings of one stream can.  The bytes read and written per frame are unchanged.  The window
+ * costs 64 / partBits extra stages: partBits of a few thousand keep it at 1 - 4 %.  The value is read on the host
+ * when a frame entry point is called (a captured graph keeps the value it was captured with); do not call the
+ * setter concurrently with launches of the same decoder.  One more VD_ERR_ARG of the frame entry points: nframes
+ * frames of maxFrameBits in parts of partBits would need more than 2^31 - 1 workgroups (ceil(ceil(W_max / Wp) / 4)
+ * per frame).  vd_decoder_kernel_name (llr 3 .. 6) names the parts per frame of such a launch. */
+
+/* VD_ERR_ARG unless partBits is 0 or a multiple of 96 in [96, 2^20] */
+int vd_set_frame_part_bits(vd_decoder* dec, size_t partBits);
+int vd_frame_part_bits(vd_decoder* dec, size_t* partBits);
+
 /* ---- the reference harness's channel source (RandBitGen | ConvolutionalEncoder | AddNoise |
  *      SoftDecisionPacker, viterbiDF.h:20-167), host and GPU ---- */
 

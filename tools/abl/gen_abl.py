@@ -38,8 +38,8 @@ TG = [
      "    if (geo.check && lane < 3 * kGuardWords) wlds[LL::guard(lane)] = kGuardPattern;\n"
      "    const uint64_t t_clk0 = (ABL & kAblClock) ? __builtin_amdgcn_s_memtime() : 0;\n"
      "    const uint64_t t_rt0 = (ABL & kAblClock) ? __builtin_amdgcn_s_memrealtime() : 0;\n\n    // per-lane LDS byte offset"),
-    ("    fair.begin((FRM ? batch + kChunks < geo.nbatch : batch + 1 < geo.nbatch) ? nullptr : geo.fair, lane);\n    // fairness progress",
-     "    if constexpr (!(ABL & kAblNoFair)) fair.begin((FRM ? batch + kChunks < geo.nbatch : batch + 1 < geo.nbatch) ? nullptr : geo.fair, lane);\n    // fairness progress"),
+    ("    fair.begin(fairOff ? nullptr : geo.fair, lane);\n    // fairness progress",
+     "    if constexpr (!(ABL & kAblNoFair)) fair.begin(fairOff ? nullptr : geo.fair, lane);\n    // fairness progress"),
     ("        if constexpr ((r / 6) % 2 == 0) {\n            vp[r] = *(lptr)(tl + aK[K] + TT::row(r));\n        }",
      "        if constexpr (ABL & kAblNoTabReads) {\n        } else if constexpr ((r / 6) % 2 == 0) {\n            vp[r] = *(lptr)(tl + aK[K] + TT::row(r));\n        }"),
     ("            const f2v e = vp[RP];", "            const f2v e = (ABL & kAblNoTabReads) ? (f2v){(float)aK[K], 1.0f} : vp[RP];"),
