@@ -263,7 +263,9 @@ const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, i
     if (llr == 2 && ch_of(d->options) == HARD) return "-";  // no punctured HARD kernels
     if (llr == 4 && ch_of(d->options) == HARD) return "-";  // ... nor punctured HARD frames
     if (llr == 6 && ch_of(d->options) == HARD) return "-";  // ... nor punctured tail-biting HARD frames
-    if (llr == 3 || llr == 4 || llr == 5 || llr == 6) {  // a frame launch (4: of punctured, 5: of tail-biting, 6: of punctured tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
+    // the int8 twins of 3 .. 6 (7 .. 10): HARD, SOFT4 and SOFT8 decoders, the punctured ones not on HARD
+    if (llr >= 7 && llr <= 10 && (ch_of(d->options) > SOFT8 || (ch_of(d->options) == HARD && (llr == 8 || llr == 10)))) return "-";
+    if (llr >= 3 && llr <= 10) {  // a frame launch (4: of punctured, 5: of tail-biting, 6: of punctured tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
         if (inputNum < 1 || inputNum > kFrmMaxBits) return "-";
         if (frame_parts_error(inputNum, nbatch, d->partBits)) return "-";  // (more workgroups than a launch can have)
         name = plan_name(plan_frames(d->options, (uint64_t)nbatch, frame_parts((uint32_t)inputNum, frame_part_words(d->partBits))),
@@ -591,16 +593,18 @@ static int frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, 
 
 // the one launch of checked arguments; pun: the frames hold the kept values of punctured frames, tb: the frames
 // are tail-biting (no pad: terminated means nothing), both: punctured tail-biting frames (vd_frames.h)
-static int launch_frames_checked(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
+// i8: the frames hold int8 values, llr_stride counts their bytes (vd_frames.h "int8 frames")
+static int launch_frames_checked(vd_decoder* d, const void* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
                                  const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
-                                 hipStream_t s, const Punct* pun = nullptr, bool tb = false)
+                                 hipStream_t s, const Punct* pun = nullptr, bool tb = false, bool i8 = false)
 {
     const int options = d->options;
     // the decoder's part length, read here, on the host: a captured graph keeps the value it was captured with
     const uint32_t partBits = d->partBits;
     if (const char* why = frame_parts_error(maxFrameBits, nframes, partBits)) return fail(VD_ERR_ARG, why);
     const LaunchPlan p = plan_frames(options, (uint64_t)nframes, frame_parts((uint32_t)maxFrameBits, frame_part_words(partBits)));
-    launch_fn f = tb && pun ? launcher_punct_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
+    launch_fn f = i8 ? launcher_byte<Launch>(pun != nullptr, tb, ch_of(options), met_of(options), out_of(options) == 1)
+                  : tb && pun ? launcher_punct_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                   : tb  ? launcher_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                   : pun ? launcher_punct_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                         : launcher_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1);
@@ -859,6 +863,81 @@ int vd_run_punct_tb_frames(vd_decoder* d, const float* rx_h, size_t rx_stride, v
     VD_HIP(hipEventRecord(d->ev0, d->stream));
     rc = launch_frames_checked(d, (const float*)d->llr_d, rx_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes, 0,
                                scale, d->stream, &pn, true);
+    if (rc != VD_OK) return rc;
+    VD_HIP(hipEventRecord(d->ev1, d->stream));
+    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
+    VD_HIP(hipStreamSynchronize(d->stream));
+    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    return VD_OK;
+}
+
+// ---- int8 frames (vd_frames.h "int8 frames"; vd_decode_tg<FRM+I8+...>, the byte twins of the four families) ----
+// the argument checks of an int8 frame decode: VD_ERR_ARG / VD_ERR_OPTIONS, or *pn filled in (null pattern: (1, 1, 1))
+static int byte_frames_args(const vd_decoder* d, const void* q, size_t q_stride, const void* output, size_t output_stride,
+                            size_t maxFrameBits, int nframes, int kind, float scale, int period, uint32_t keep0, uint32_t keep1,
+                            bool device, Punct* pn, bool* pun)
+{
+    if (!d || !q || !output) return fail(VD_ERR_ARG, "null argument");
+    if (const char* why = byte_frame_args_error(device ? (uint64_t)(uintptr_t)q : 0, q_stride, output_stride, maxFrameBits, nframes,
+                                                kind, scale, period, keep0, keep1, d->partBits))
+        return fail(VD_ERR_ARG, why);
+    *pun = !byte_frames_unpunctured(period, keep0, keep1);
+    const int ch = ch_of(d->options);
+    if (ch != HARD && ch != SOFT4 && ch != SOFT8)
+        return fail(VD_ERR_OPTIONS, "int8 frames on a SOFT16 or FP32 decoder: an int8 value carries nothing that a SOFT8 "
+                                    "decoder does not use; use HARD, SOFT4 or SOFT8");
+    if (ch == HARD && kind == kByteFramesOpen)
+        return fail(VD_ERR_OPTIONS, "open frames on a HARD decoder: the stages after an open frame are erasures, and HARD's "
+                                    "v > 0 ? 1 : 0 has no neutral code; terminate the frames or use SOFT4 or SOFT8");
+    if (ch == HARD && *pun)
+        return fail(VD_ERR_OPTIONS, "punctured frames on a HARD decoder: a punctured value must decode as code 0 = value 0, "
+                                    "and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4 or SOFT8");
+    *pn = punct_make(period, keep0, keep1);
+    return VD_OK;
+}
+
+int vd_run_device_byte_frames(vd_decoder* d, const int8_t* q_d, size_t q_stride, void* output_d, size_t output_stride,
+                              const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int kind, float scale,
+                              int period, uint32_t keep0, uint32_t keep1, void* stream)
+{
+    Punct pn;
+    bool pun;
+    int rc = byte_frames_args(d, q_d, q_stride, output_d, output_stride, maxFrameBits, nframes, kind, scale, period, keep0,
+                              keep1, true, &pn, &pun);
+    if (rc != VD_OK) return rc;
+    return launch_frames_checked(d, q_d, q_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes,
+                                 kind == kByteFramesTerminated, scale, (hipStream_t)stream, pun ? &pn : nullptr,
+                                 kind == kByteFramesTailbiting, true);
+}
+
+// the host buffers laid out like the device ones (vd_run_frames): the last frame's part ends with the bytes of its
+// maxFrameBits stages; the staging buffers are the decoder's, the lengths ride behind the bytes
+int vd_run_byte_frames(vd_decoder* d, const int8_t* q_h, size_t q_stride, void* output_h, size_t output_stride,
+                       const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int kind, float scale, int period,
+                       uint32_t keep0, uint32_t keep1, float* kernel_ms)
+{
+    Punct pn;
+    bool pun;
+    int rc = byte_frames_args(d, q_h, q_stride, output_h, output_stride, maxFrameBits, nframes, kind, scale, period, keep0,
+                              keep1, false, &pn, &pun);
+    if (rc != VD_OK) return rc;
+    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
+    const size_t inB = (size_t)(nframes - 1) * q_stride + byte_pfrm_bytes(pn, (uint32_t)maxFrameBits);
+    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
+    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
+    VD_HIP(hipSetDevice(d->device));
+    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
+    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
+    if (rc != VD_OK) return rc;
+    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
+    if (inB) VD_HIP(hipMemcpyAsync(d->llr_d, q_h, inB, hipMemcpyHostToDevice, d->stream));
+    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
+    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
+    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
+    VD_HIP(hipEventRecord(d->ev0, d->stream));
+    rc = launch_frames_checked(d, d->llr_d, q_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes,
+                               kind == kByteFramesTerminated, scale, d->stream, pun ? &pn : nullptr,
+                               kind == kByteFramesTailbiting, true);
     if (rc != VD_OK) return rc;
     VD_HIP(hipEventRecord(d->ev1, d->stream));
     VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));

@@ -45,9 +45,11 @@ VD_FRAMES_HD bool frame_pad_stage(uint32_t p, uint32_t end) { return p < kFrmLea
 VD_FRAMES_HD bool frame_pad_group(uint32_t g0, uint32_t end) { return g0 < kFrmLead || g0 + kFrmGroup > end; }
 // byte offset of stage p's two floats against a resource of 8 S bytes at the frame's first float:
 // inside the range exactly for 26 <= p < 26 + S (p <= kFrmMaxBits + a few groups: 8 p stays far below 2^31)
+// (VB: the bytes of a channel value, 4 for floats; 1 for the int8 frames at the end of this header)
+template <uint32_t VB = 4>
 VD_FRAMES_HD uint32_t frame_offset(uint32_t p)
 {
-    const uint32_t o = 8u * (p - kFrmLead);  // wraps for p < 26
+    const uint32_t o = 2u * VB * (p - kFrmLead);  // wraps for p < 26
     return o < kFrmOutside ? o : kFrmOutside;
 }
 
@@ -97,11 +99,12 @@ inline const char* frame_args_error(uint64_t llr_addr, uint64_t llr_stride, uint
 // tests/cxx/punct_frames_check.cpp checks the helpers below against a plain enumeration.
 
 // the received bytes of a punctured frame of S <= kFrmMaxBits stages: 4 punct_len(2 S), at most 8 MiB
+template <uint32_t VB = 4>
 VD_FRAMES_HD uint32_t pfrm_bytes(const Punct& pn, uint32_t S)
 {
     uint32_t q, r;
     punct_divmod(pn, S, q, r);
-    return 4u * (q * pn.kp + punct_before(pn, r));
+    return VB * (q * pn.kp + punct_before(pn, r));
 }
 // the group from padded stage g0 (a multiple of kFrmGroup): its first frame stage t0, and the lanes s < lead
 // that lie before the frame
@@ -113,11 +116,12 @@ VD_FRAMES_HD constexpr PfrmGroup pfrm_group(uint32_t g0)
     return g0 < kFrmLead ? PfrmGroup{0u, kFrmLead - g0} : PfrmGroup{g0 - kFrmLead, 0u};
 }
 // byte offset of float q0 Kp, (q0, r0) = divmod(t0, period); *r0 = t0 % period
+template <uint32_t VB = 4>
 VD_FRAMES_HD uint32_t pfrm_base(const Punct& pn, uint32_t t0, uint32_t* r0)
 {
     uint32_t q0;
     punct_divmod(pn, t0, q0, *r0);
-    return q0 * (pn.kp * 4u);
+    return q0 * (pn.kp * VB);
 }
 // the byte offsets of the two values of lane s (< kFrmGroup) of the group (base4, r0, lead) against the frame's
 // resource: inside the range exactly for a kept value of a frame stage < S
@@ -128,6 +132,7 @@ struct PfrmOff {
 // (v_mul_u32_u24 / v_mad_u32_u24, which ignore the upper bits: the masks cost no instruction) where the 32-bit
 // v_mul_lo_u32 issues at a quarter of the rate -- six of those per group were most of this path's cost
 VD_FRAMES_HD uint32_t pfrm_mul24(uint32_t a, uint32_t b) { return (a & 0xFFFFFFu) * (b & 0xFFFFFFu); }
+template <uint32_t VB = 4>
 VD_FRAMES_HD PfrmOff pfrm_offsets(const Punct& pn, uint32_t base4, uint32_t r0, uint32_t lead, uint32_t s)
 {
     const uint32_t before = s < lead ? kFrmOutside : 0u;
@@ -137,8 +142,8 @@ VD_FRAMES_HD PfrmOff pfrm_offsets(const Punct& pn, uint32_t base4, uint32_t r0, 
     const uint32_t dq = pfrm_mul24(x, pn.m16) >> 16;
     const uint32_t r = x - pfrm_mul24(dq, pn.period);
     const uint32_t has0 = (pn.keep0 >> r) & 1u, has1 = (pn.keep1 >> r) & 1u;
-    const uint32_t b = base4 + pfrm_mul24(dq, 4u * pn.kp) + (punct_before(pn, r) << 2);
-    return {b | ((has0 ^ 1u) * kFrmOutside) | before, (b + (has0 << 2)) | ((has1 ^ 1u) * kFrmOutside) | before};
+    const uint32_t b = base4 + pfrm_mul24(dq, VB * pn.kp) + punct_before(pn, r) * VB;
+    return {b | ((has0 ^ 1u) * kFrmOutside) | before, (b + has0 * VB) | ((has1 ^ 1u) * kFrmOutside) | before};
 }
 
 // The argument checks of vd_run_device_punct_frames (all VD_ERR_ARG): the message, or null when the arguments are
@@ -220,14 +225,17 @@ VD_FRAMES_HD uint32_t tb_lane_stage(uint32_t r0, uint32_t s, uint32_t S, uint32_
     return tb_turns_stage(x, S, m16);
 }
 // byte offset of the two floats of frame stage t (< S) against the frame's resource: offset + 8 <= 8 S
-VD_FRAMES_HD uint32_t tb_offset(uint32_t t) { return 8u * t; }
+template <uint32_t VB = 4>
+VD_FRAMES_HD uint32_t tb_offset(uint32_t t) { return 2u * VB * t; }
 // ... of lane s of a group that does not wrap (g0 >= 26, g0 + 96 - 26 <= S): frame stage g0 - 26 + s
-VD_FRAMES_HD uint32_t tb_offset_inside(uint32_t g0, uint32_t s) { return 8u * (g0 - kFrmLead + s); }
+template <uint32_t VB = 4>
+VD_FRAMES_HD uint32_t tb_offset_inside(uint32_t g0, uint32_t s) { return 2u * VB * (g0 - kFrmLead + s); }
 // the map as the kernel evaluates it: the offset of stage g0 + s of the extended stream
+template <uint32_t VB = 4>
 VD_FRAMES_HD uint32_t tb_stage_offset(uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
 {
-    if (!tb_wrap_group(g0, S)) return tb_offset_inside(g0, s);
-    return tb_offset(tb_lane_stage(tb_group_r0(g0, S, rc.m32), s, S, rc.m16));
+    if (!tb_wrap_group(g0, S)) return tb_offset_inside<VB>(g0, s);
+    return tb_offset<VB>(tb_lane_stage(tb_group_r0(g0, S, rc.m32), s, S, rc.m16));
 }
 
 // The argument checks of vd_run_device_tb_frames (all VD_ERR_ARG): the message, or null when the arguments are
@@ -280,6 +288,7 @@ constexpr uint32_t kPtbInside = 0, kPtbWrap = 1, kPtbTurns = 2;
 struct PtbGroup {
     uint32_t mode, rs, base4, r0;
 };
+template <uint32_t VB = 4>
 VD_FRAMES_HD PtbGroup ptb_group(const Punct& pn, uint32_t g0, uint32_t S, const TbRecip& rc)
 {
     PtbGroup g = {kPtbTurns, 0u, 0u, 0u};
@@ -288,13 +297,14 @@ VD_FRAMES_HD PtbGroup ptb_group(const Punct& pn, uint32_t g0, uint32_t S, const 
     if (wrap && S < kFrmGroup) return g;
     g.mode = wrap ? kPtbWrap : kPtbInside;
     uint32_t r0;
-    g.base4 = VD_FRAMES_UNIFORM(pfrm_base(pn, VD_FRAMES_UNIFORM(wrap ? g.rs : g0 - kFrmLead), &r0));
+    g.base4 = VD_FRAMES_UNIFORM(pfrm_base<VB>(pn, VD_FRAMES_UNIFORM(wrap ? g.rs : g0 - kFrmLead), &r0));
     g.r0 = VD_FRAMES_UNIFORM(r0);
     return g;
 }
 #undef VD_FRAMES_UNIFORM
 // the byte offsets of the two values of lane s (< kFrmGroup) of the group g against the frame's resource: inside
 // the range exactly for a kept value (m16: tb_recip(S).m16, used for S < 96 only)
+template <uint32_t VB = 4>
 VD_FRAMES_HD PfrmOff ptb_offsets(const Punct& pn, const PtbGroup& g, uint32_t s, uint32_t S, uint32_t m16)
 {
     uint32_t b = g.base4, r = g.r0, ls = s;
@@ -308,12 +318,13 @@ VD_FRAMES_HD PfrmOff ptb_offsets(const Punct& pn, const PtbGroup& g, uint32_t s,
     } else if (g.mode == kPtbTurns) {
         ls = tb_turns_stage(g.rs + s, S, m16);  // tb_lane_stage for S < 96 (ptb_group): t < 96; b = r = 0
     }
-    return pfrm_offsets(pn, b, r, 0u, ls);
+    return pfrm_offsets<VB>(pn, b, r, 0u, ls);
 }
 // the map as the kernel evaluates it: the offsets of the two values of stage g0 + s of the extended stream
+template <uint32_t VB = 4>
 VD_FRAMES_HD PfrmOff ptb_stage_offsets(const Punct& pn, uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
 {
-    return ptb_offsets(pn, ptb_group(pn, g0, S, rc), s, S, rc.m16);
+    return ptb_offsets<VB>(pn, ptb_group<VB>(pn, g0, S, rc), s, S, rc.m16);
 }
 
 // The argument checks of vd_run_device_punct_tb_frames (all VD_ERR_ARG): the message, or null when the arguments
@@ -405,6 +416,78 @@ inline const char* frame_parts_error(uint64_t maxFrameBits, int nframes, uint64_
     if (frame_parts_grid((uint64_t)nframes, (uint32_t)maxFrameBits, (uint32_t)partBits) > kFrmMaxGrid)
         return "nframes frames in parts of partBits need more than 2^31 - 1 workgroups";
     return nullptr;
+}
+
+// ---------------------------------------------------------------- int8 frames (channel ids kI8 + kFrm + ... + format)
+// The four families above on frames of int8 channel values, one byte each in mother order and plain memory order
+// (not the packed words of the stream decodes): a frame of S stages under a pattern holds punct_len(2 S) bytes, and
+// its decode is the float family's decode of the frame (float)q -- the same padded or extended stream, pad value,
+// erasures, phase rule and parts.  Only the byte offsets differ, the helpers above with VB = 1:
+//   unpunctured (pattern (1, 1, 1)): a stage's two values are one aligned 16-bit access (first encoder output in
+//     the low byte) against a resource of 2 S bytes.  Stage p of the padded stream reads at byte_frame_offset(p) =
+//     2 (p - 26) with frame_offset's clamp: it wraps to 2^32 - 2 (26 - p) for p < 26, and for p = 25 the end of the
+//     2-byte access, 2^32, is 0 in 32 bits as the end of the 8-byte access is, so such a lane reads at kFrmOutside,
+//     whose end 2^31 + 2 lies past every range (<= 2 kFrmMaxBits) with no wrap.  For p >= 26, 2 p < 2^22.  A
+//     tail-biting frame stage t reads at byte_tb_offset(t) = 2 t, offset + 2 <= 2 S;
+//   punctured: single-byte accesses against a resource of byte_pfrm_bytes = punct_len(2 S) <= 2^21 bytes, at the
+//     kept index itself.  The offsets are a quarter of the float ones, so what the float maps rely on holds with
+//     room to spare: base4 = q0 Kp <= 2 S < 2^22 and every kept offset stay below 2^24 (the 24-bit products x m16 <
+//     2^23, dq Kp < 112 * 32, dq period < 112 * 16 are those of pfrm_offsets, VB = 1 only drops a factor), a
+//     punctured value or lead stage takes kFrmOutside and kFrmOutside | offset + 1 does not wrap in 32 bits, and a
+//     stage >= S lands at or past the range's end since the kept indices grow with the stage.
+// An out-of-range 8- or 16-bit buffer load returns zero as a dword load does; tests/test_gpu_byte_frames.py settles
+// it on the device (frames of one stage, neighbours of other frames' extreme values).
+// tests/cxx/byte_frames_check.cpp checks the helpers below against a plain enumeration.
+constexpr int kByteFramesOpen = 0, kByteFramesTerminated = 1, kByteFramesTailbiting = 2;  // vd_capi.h VD_FRAMES_*
+VD_FRAMES_HD uint32_t byte_frame_offset(uint32_t p) { return frame_offset<1>(p); }
+VD_FRAMES_HD uint32_t byte_tb_offset(uint32_t t) { return tb_offset<1>(t); }
+VD_FRAMES_HD uint32_t byte_tb_stage_offset(uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
+{
+    return tb_stage_offset<1>(g0, s, S, rc);
+}
+VD_FRAMES_HD uint32_t byte_pfrm_bytes(const Punct& pn, uint32_t S) { return pfrm_bytes<1>(pn, S); }
+VD_FRAMES_HD uint32_t byte_pfrm_base(const Punct& pn, uint32_t t0, uint32_t* r0) { return pfrm_base<1>(pn, t0, r0); }
+VD_FRAMES_HD PfrmOff byte_pfrm_offsets(const Punct& pn, uint32_t base1, uint32_t r0, uint32_t lead, uint32_t s)
+{
+    return pfrm_offsets<1>(pn, base1, r0, lead, s);
+}
+VD_FRAMES_HD PfrmOff byte_ptb_stage_offsets(const Punct& pn, uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
+{
+    return ptb_stage_offsets<1>(pn, g0, s, S, rc);
+}
+// the pattern that selects the unpunctured kernels (any other valid pattern, a keep-all one of a longer period
+// too, selects the punctured ones)
+VD_FRAMES_HD bool byte_frames_unpunctured(int period, uint32_t keep0, uint32_t keep1)
+{
+    return period == 1 && keep0 == 1u && keep1 == 1u;
+}
+
+// The argument checks of vd_run_device_byte_frames (all VD_ERR_ARG): the message, or null when the arguments are
+// good.  q_addr: the address of the first frame's first byte; partBits: the decoder's part length.
+inline const char* byte_frame_args_error(uint64_t q_addr, uint64_t q_stride, uint64_t output_stride, uint64_t maxFrameBits,
+                                         int nframes, int kind, float scale, int period, uint32_t keep0, uint32_t keep1,
+                                         uint64_t partBits)
+{
+    float pad;
+    if (kind != kByteFramesOpen && kind != kByteFramesTerminated && kind != kByteFramesTailbiting)
+        return "kind must be VD_FRAMES_OPEN, VD_FRAMES_TERMINATED or VD_FRAMES_TAILBITING";
+    if (!punct_valid(period, keep0, keep1))
+        return "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
+    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
+    if (nframes < 1) return "nframes must be >= 1";
+    if (kind == kByteFramesTailbiting) {
+        if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
+    } else if (!frame_pad(scale, &pad)) {
+        return "scale must be finite and > 0 (and -65536 / scale finite)";
+    }
+    if (byte_frames_unpunctured(period, keep0, keep1) && ((q_addr | q_stride) & 1))
+        return "q_d and q_stride must be multiples of 2 bytes under pattern (1, 1, 1): a stage is one 16-bit access";
+    if (output_stride & 3) return "output_stride must be a multiple of 4 bytes";
+    if (nframes > 1 && q_stride < byte_pfrm_bytes(punct_make(period, keep0, keep1), (uint32_t)maxFrameBits))
+        return "q_stride smaller than vd_punctured_len(2 * maxFrameBits): frames would overlap";
+    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
+        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
+    return frame_parts_error(maxFrameBits, nframes, partBits);
 }
 
 }  // namespace vd

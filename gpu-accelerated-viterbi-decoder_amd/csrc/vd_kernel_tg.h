@@ -51,6 +51,9 @@ constexpr int kFrm = 24;
 // around the frame are the frame's own other end, a wrap in the loads (TgInTbf; vd_frames.h)
 // kFrm + kTb + kPun + base = the kept float values of independent punctured tail-biting frames (TgInPtb)
 constexpr int kTb = 32;
+// kI8 + one of the four frame ids above (HARD, SOFT4, SOFT8) = the same frames held as int8 channel values, one
+// byte each: byte-wide loads widened to the float pair of the family's float kernel (TgInI8, "int8 frames" below)
+constexpr int kI8 = 64;
 
 template <int CH>
 struct TgFmt {
@@ -691,10 +694,28 @@ template <class T, class = void>
 struct HasFrm : std::false_type {};
 template <class T>
 struct HasFrm<T, std::void_t<decltype(T::FRM)>> : std::bool_constant<T::FRM> {};
+// The loads of the four frame families take I8 (int8 frames, "int8 frames" below): the same offsets in units of one
+// byte (vd_frames.h, VB = 1), a stage's pair as one 16-bit load or a kept value as one 8-bit load, returned unwidened:
+// the loaded bits as they came, in the registers of the float pair (tg_i8_widen makes the floats where they are used).
+// a stage's two values at byte offset o: two floats, or (I8) its two int8 values in the low half of .x
+template <bool I8>
+__device__ __forceinline__ float2 tg_pair_load(__amdgpu_buffer_rsrc_t rs, uint32_t o)
+{
+    if constexpr (I8) return make_float2(__builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rs, o, 0, 0)), 0.0f);
+    else return TgIn<FP32>::template load<0>(rs, o);
+}
+// one kept value at byte offset o: a float, or (I8) an int8 value in the low byte
+template <bool I8>
+__device__ __forceinline__ float tg_value_load(__amdgpu_buffer_rsrc_t rs, uint32_t o)
+{
+    if constexpr (I8) return __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, o, 0, 0));
+    else return __builtin_bit_cast(float, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0));
+}
 // the two values of stage p of the padded stream of the frame whose resource is rs (zero for a virtual stage)
+template <bool I8 = false>
 __device__ __forceinline__ float2 tg_frm_load(__amdgpu_buffer_rsrc_t rs, uint32_t p)
 {
-    return TgIn<FP32>::template load<0>(rs, frame_offset(p));
+    return tg_pair_load<I8>(rs, frame_offset<I8 ? 1 : 4>(p));
 }
 
 // ---------------------------------------------------------------- punctured frames (vd_frames.h "punctured frames")
@@ -722,12 +743,13 @@ struct HasPfr : std::false_type {};
 template <class T>
 struct HasPfr<T, std::void_t<decltype(T::PFR)>> : std::bool_constant<T::PFR> {};
 // the two values of lane stage s (< 96) of the group from padded stage g0 of the frame whose resource is rs
+template <bool I8 = false>
 __device__ __forceinline__ float2 tg_pfr_load(__amdgpu_buffer_rsrc_t rs, const Punct& pn, uint32_t base4, uint32_t r0,
                                               uint32_t lead, uint32_t s)
 {
-    const PfrmOff o = pfrm_offsets(pn, base4, r0, lead, s);
-    const uint32_t x = __builtin_amdgcn_raw_buffer_load_b32(rs, o.o0, 0, 0), y = __builtin_amdgcn_raw_buffer_load_b32(rs, o.o1, 0, 0);
-    return make_float2(__builtin_bit_cast(float, x), __builtin_bit_cast(float, y));
+    const PfrmOff o = pfrm_offsets<I8 ? 1 : 4>(pn, base4, r0, lead, s);
+    const float x = tg_value_load<I8>(rs, o.o0), y = tg_value_load<I8>(rs, o.o1);
+    return make_float2(x, y);
 }
 
 // ---------------------------------------------------------------- tail-biting frames (vd_frames.h "tail-biting frames")
@@ -756,20 +778,22 @@ template <class T>
 struct HasTbf<T, std::void_t<decltype(T::TBF)>> : std::bool_constant<T::TBF> {};
 // the values of lane stages sa and sb (< 96) of the group from extended stage g0 (wave-uniform) of the tail-biting
 // frame of S stages (wave-uniform, with its reciprocals rc) whose resource is rs: one branch for both loads
+template <bool I8 = false>
 __device__ __forceinline__ void tg_tbf_load(__amdgpu_buffer_rsrc_t rs, uint32_t g0, uint32_t sa, uint32_t sb, uint32_t S,
                                             const TbRecip& rc, float2& ra, float2& rb)
 {
+    constexpr uint32_t VB = I8 ? 1 : 4;
     uint32_t oa, ob;
     if (tb_wrap_group(g0, S)) {
         const uint32_t r0 = __builtin_amdgcn_readfirstlane(tb_group_r0(g0, S, rc.m32));
-        oa = tb_offset(tb_lane_stage(r0, sa, S, rc.m16));
-        ob = tb_offset(tb_lane_stage(r0, sb, S, rc.m16));
+        oa = tb_offset<VB>(tb_lane_stage(r0, sa, S, rc.m16));
+        ob = tb_offset<VB>(tb_lane_stage(r0, sb, S, rc.m16));
     } else {
-        oa = tb_offset_inside(g0, sa);
-        ob = tb_offset_inside(g0, sb);
+        oa = tb_offset_inside<VB>(g0, sa);
+        ob = tb_offset_inside<VB>(g0, sb);
     }
-    ra = TgIn<FP32>::template load<0>(rs, oa);
-    rb = TgIn<FP32>::template load<0>(rs, ob);
+    ra = tg_pair_load<I8>(rs, oa);
+    rb = tg_pair_load<I8>(rs, ob);
 }
 
 // ---------------------------------------------------------------- punctured tail-biting frames (vd_frames.h)
@@ -798,15 +822,61 @@ template <class T>
 struct HasPtb<T, std::void_t<decltype(T::PTB)>> : std::bool_constant<T::PTB> {};
 // the values of lane stages sa and sb (< 96) of the group from extended stage g0 (wave-uniform) of the punctured
 // tail-biting frame of S stages (wave-uniform, with its reciprocals rc) whose resource is rs: one form for both
+template <bool I8 = false>
 __device__ __forceinline__ void tg_ptb_load(__amdgpu_buffer_rsrc_t rs, const Punct& pn, uint32_t g0, uint32_t sa, uint32_t sb,
                                             uint32_t S, const TbRecip& rc, float2& ra, float2& rb)
 {
-    const PtbGroup g = ptb_group(pn, g0, S, rc);
-    const PfrmOff oa = ptb_offsets(pn, g, sa, S, rc.m16), ob = ptb_offsets(pn, g, sb, S, rc.m16);
-    const uint32_t xa = __builtin_amdgcn_raw_buffer_load_b32(rs, oa.o0, 0, 0), ya = __builtin_amdgcn_raw_buffer_load_b32(rs, oa.o1, 0, 0);
-    const uint32_t xb = __builtin_amdgcn_raw_buffer_load_b32(rs, ob.o0, 0, 0), yb = __builtin_amdgcn_raw_buffer_load_b32(rs, ob.o1, 0, 0);
-    ra = make_float2(__builtin_bit_cast(float, xa), __builtin_bit_cast(float, ya));
-    rb = make_float2(__builtin_bit_cast(float, xb), __builtin_bit_cast(float, yb));
+    constexpr uint32_t VB = I8 ? 1 : 4;
+    const PtbGroup g = ptb_group<VB>(pn, g0, S, rc);
+    const PfrmOff oa = ptb_offsets<VB>(pn, g, sa, S, rc.m16), ob = ptb_offsets<VB>(pn, g, sb, S, rc.m16);
+    const float xa = tg_value_load<I8>(rs, oa.o0), ya = tg_value_load<I8>(rs, oa.o1);
+    const float xb = tg_value_load<I8>(rs, ob.o0), yb = tg_value_load<I8>(rs, ob.o1);
+    ra = make_float2(xa, ya);
+    rb = make_float2(xb, yb);
+}
+
+// ---------------------------------------------------------------- int8 frames (vd_frames.h "int8 frames")
+// kI8 + a frame id + base (HARD, SOFT4, SOFT8) = the family's frames held as int8 channel values: HARD, SOFT4 and
+// SOFT8 only, since an int8 value carries nothing that a SOFT8 decoder does not use.  Only the loads differ from the
+// float twin.  One resource per frame over its bytes (2 S, or the received bytes of a punctured frame), the float
+// twin's offsets in bytes, and per stage one buffer_load_ushort (both values, the first in the low byte) or per kept
+// value one 8-bit load: a quarter of the float twin's traffic.  Virtual stages, punctured values and stages past the
+// frame read zero through the range check as they do there.  What is loaded waits a group in the float pair's
+// registers as it came (one VGPR per stage where the twin holds two) and is widened where the values are used, at
+// the group head before the pad select (tg_i8_widen: one sign-extending byte convert per value), so the prefetch is
+// not waited on early.  From there on -- the scale, the quantisation, the pad, the table rows, the cores, the ring,
+// the traceback, the parts and the fairness rule -- the kernel is the float twin's, TgInLlr<BASE>.
+template <class FAM>
+struct TgInI8 : FAM {
+    static constexpr bool I8 = true;
+};
+template <> struct TgIn<kI8 + kFrm + HARD> : TgInI8<TgInFrm<HARD>> {};
+template <> struct TgIn<kI8 + kFrm + SOFT4> : TgInI8<TgInFrm<SOFT4>> {};
+template <> struct TgIn<kI8 + kFrm + SOFT8> : TgInI8<TgInFrm<SOFT8>> {};
+template <> struct TgIn<kI8 + kFrm + kPun + SOFT4> : TgInI8<TgInPfr<SOFT4>> {};
+template <> struct TgIn<kI8 + kFrm + kPun + SOFT8> : TgInI8<TgInPfr<SOFT8>> {};
+template <> struct TgIn<kI8 + kFrm + kTb + HARD> : TgInI8<TgInTbf<HARD>> {};
+template <> struct TgIn<kI8 + kFrm + kTb + SOFT4> : TgInI8<TgInTbf<SOFT4>> {};
+template <> struct TgIn<kI8 + kFrm + kTb + SOFT8> : TgInI8<TgInTbf<SOFT8>> {};
+template <> struct TgIn<kI8 + kFrm + kTb + kPun + SOFT4> : TgInI8<TgInPtb<SOFT4>> {};
+template <> struct TgIn<kI8 + kFrm + kTb + kPun + SOFT8> : TgInI8<TgInPtb<SOFT8>> {};
+template <class T, class = void>
+struct HasI8 : std::false_type {};
+template <class T>
+struct HasI8<T, std::void_t<decltype(T::I8)>> : std::bool_constant<T::I8> {};
+// the float pair of what an int8 load left in r: PAIR: both values in the low half of .x (first value in the low
+// byte), else one value in the low byte of .x and of .y
+// (one sign-extending byte convert each, as TgIn<SOFT8>::s01: left to itself the compiler sign-extends with v_bfe_i32
+// first and shifts byte 1 down, five VALU ops a pair instead of two)
+template <bool PAIR>
+__device__ __forceinline__ float2 tg_i8_widen(float2 r)
+{
+    const uint32_t a = __builtin_bit_cast(uint32_t, r.x), b = __builtin_bit_cast(uint32_t, r.y);
+    float x, y;
+    asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0" : "=v"(x) : "v"(a));
+    if constexpr (PAIR) asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1" : "=v"(y) : "v"(a));
+    else asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0" : "=v"(y) : "v"(b));
+    return make_float2(x, y);
 }
 
 // ---------------------------------------------------------------- segment launches
@@ -948,7 +1018,9 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     constexpr bool PFR = HasPfr<IN>::value;  // ... of the kept values of a punctured frame (tg_pfr_load)
     constexpr bool PTB = HasPtb<IN>::value;  // ... of a punctured tail-biting frame: both maps (tg_ptb_load)
     uint32_t pfrB = 0;                       // its received bytes (wave-uniform)
-    if constexpr (PFR || PTB) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes(geo.pun, frmS));
+    constexpr bool I8 = HasI8<IN>::value;    // ... held as int8 values: byte-wide loads (tg_i8_widen)
+    constexpr uint32_t VB = I8 ? 1 : 4;      // bytes of a channel value in the frame's buffer
+    if constexpr (PFR || PTB) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes<VB>(geo.pun, frmS));
     const uint32_t batch = FRM ? frmF : geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
     const void* const in = (const char*)in_all + batch * geo.inStride;
     void* const out = (char*)out_all + batch * geo.outStride;
@@ -1081,26 +1153,26 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         // q0 = r0 = 0), or a later part's (no lead stage, frame stage fst - 26)
         const PfrmGroup pg = pfrm_group(fst);
         uint32_t r0;
-        const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
+        const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base<VB>(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
         r0 = __builtin_amdgcn_readfirstlane(r0);
         const uint32_t lead = __builtin_amdgcn_readfirstlane(pg.lead);
-        rA = tg_pfr_load(rs, geo.pun, base4, r0, lead, (uint32_t)sA);
-        rB = tg_pfr_load(rs, geo.pun, base4, r0, lead, (uint32_t)sB);
+        rA = tg_pfr_load<I8>(rs, geo.pun, base4, r0, lead, (uint32_t)sA);
+        rB = tg_pfr_load<I8>(rs, geo.pun, base4, r0, lead, (uint32_t)sB);
     } else if constexpr (PTB) {  // one resource for the whole frame: its received bytes; the frame's group 0 wraps its lead
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)pfrB, 0x00020000);
-        tg_ptb_load(rs, geo.pun, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+        tg_ptb_load<I8>(rs, geo.pun, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
     } else if constexpr (PUN) {
         uint32_t r0;
         rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
         rA = tg_pun_load(rs, geo.pun, r0, (uint32_t)sA);
         rB = tg_pun_load(rs, geo.pun, r0, (uint32_t)sB);
-    } else if constexpr (TBF) {  // one resource for the whole frame: its 8 frmS bytes; the frame's group 0 wraps its lead
-        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(8u * frmS), 0x00020000);
-        tg_tbf_load(rs, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
-    } else if constexpr (FRM) {  // one resource for the whole frame: its 8 frmS bytes
-        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(8u * frmS), 0x00020000);
-        rA = tg_frm_load(rs, fst + (uint32_t)sA);
-        rB = tg_frm_load(rs, fst + (uint32_t)sB);
+    } else if constexpr (TBF) {  // one resource for the whole frame: its 8 frmS bytes (I8: 2 frmS); the frame's group 0 wraps its lead
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(2u * VB * frmS), 0x00020000);
+        tg_tbf_load<I8>(rs, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+    } else if constexpr (FRM) {  // one resource for the whole frame: its 8 frmS bytes (I8: 2 frmS)
+        rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)(2u * VB * frmS), 0x00020000);
+        rA = tg_frm_load<I8>(rs, fst + (uint32_t)sA);
+        rB = tg_frm_load<I8>(rs, fst + (uint32_t)sB);
     } else {
         rs = tg_rsrc<CH>(in, start + 32ull * j0, availB);
         rA = IN::template load<0>(rs, vo1);
@@ -1258,6 +1330,10 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     for (uint32_t j = j0;; j += 3) {
         // group head: the table from the inputs loaded one group ago, the next group's loads, then the
         // fairness board (its load returns during this group; nothing here waits on it)
+        if constexpr (I8) {  // int8 frames: the float pair of what the loads of a group ago left
+            rA = tg_i8_widen<!(PFR || PTB)>(rA);
+            rB = tg_i8_widen<!(PFR || PTB)>(rB);
+        }
         if constexpr (FRM && !TBF && !PTB) {
             // the pad value in the lanes of this group's pad stages (vd_frames.h): a uniform branch that the
             // groups inside the frame skip
@@ -1295,14 +1371,14 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             __builtin_assume(g0n >= kFrmGroup);  // (no lead stage: pg.lead folds to 0)
             const PfrmGroup pg = pfrm_group(g0n);
             uint32_t r0;
-            const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
+            const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base<VB>(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
             r0 = __builtin_amdgcn_readfirstlane(r0);
-            rA = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sA);
-            rB = tg_pfr_load(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sB);
+            rA = tg_pfr_load<I8>(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sA);
+            rB = tg_pfr_load<I8>(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sB);
         } else if constexpr (PTB) {  // the next group's kept values of the extended stream: the frame, wrapped
             const uint32_t g0n = fst + 32u * (j + 3);
             __builtin_assume(g0n >= kFrmGroup);  // (no lead: tb_wrap_group and tb_group_r0 fold to their g0 >= 26 forms)
-            tg_ptb_load(rs, geo.pun, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+            tg_ptb_load<I8>(rs, geo.pun, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
         } else if constexpr (PUN) {  // the next group's received values, at the offsets of its own r0
             uint32_t r0;
             rs = tg_rsrc_pun(in, start + 32ull * (j + 3), availB, geo.pun, &r0);
@@ -1311,10 +1387,10 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         } else if constexpr (TBF) {  // the next group's stages of the extended stream: the frame, wrapped
             const uint32_t g0n = fst + 32u * (j + 3);
             __builtin_assume(g0n >= kFrmGroup);  // (no lead: tb_wrap_group and tb_group_r0 fold to their g0 >= 26 forms)
-            tg_tbf_load(rs, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+            tg_tbf_load<I8>(rs, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
         } else if constexpr (FRM) {  // the next group's stages of the padded stream
-            rA = tg_frm_load(rs, fst + 32u * (j + 3) + (uint32_t)sA);
-            rB = tg_frm_load(rs, fst + 32u * (j + 3) + (uint32_t)sB);
+            rA = tg_frm_load<I8>(rs, fst + 32u * (j + 3) + (uint32_t)sA);
+            rB = tg_frm_load<I8>(rs, fst + 32u * (j + 3) + (uint32_t)sB);
         } else
         {  // the next group's input words
             rs = tg_rsrc<CH>(in, start + 32ull * (j + 3), availB);

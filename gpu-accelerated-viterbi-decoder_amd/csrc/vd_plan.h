@@ -220,6 +220,48 @@ typename L::fn launcher_punct_tb_frames(int ch, int me, bool o16)
     return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
 }
 
+// int8 frames (channel ids kI8 + the family's id + format, vd_kernel_tg.h; vd_frames.h "int8 frames"): the byte twins
+// of the four frame tables above for HARD, SOFT4 and SOFT8 -- 8 pairs x {O32, O16} for frames and tail-biting frames,
+// the 5 without HARD for the two punctured families: 52 kernels, in four tables of their own, planned by plan_frames.
+#define VD_BYTE_PAIRS(X) X(HARD, B32) X(HARD, B16) X(HARD, F16) VD_BYTE_PUN_PAIRS(X)
+#define VD_BYTE_PUN_PAIRS(X) X(SOFT4, B32) X(SOFT4, B16) X(SOFT4, F16) X(SOFT8, B32) X(SOFT8, B16)
+#define VD_BYTE_TABLE(NAME, PAIRS)                                                           \
+    template <class L>                                                                       \
+    typename L::fn NAME(int ch, int me, bool o16)                                            \
+    {                                                                                        \
+        struct Table {                                                                       \
+            typename L::fn at[3][3][2] = {};                                                 \
+            Table()                                                                          \
+            {                                                                                \
+                PAIRS(VD_X)                                                                  \
+            }                                                                                \
+        };                                                                                   \
+        static const Table t;                                                                \
+        return ch >= 0 && ch < 3 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;         \
+    }
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + C, M, 16>;
+VD_BYTE_TABLE(launcher_byte_frames, VD_BYTE_PAIRS)
+#undef VD_X
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + kPun + C, M, 16>;
+VD_BYTE_TABLE(launcher_byte_punct_frames, VD_BYTE_PUN_PAIRS)
+#undef VD_X
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + kTb + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + kTb + C, M, 16>;
+VD_BYTE_TABLE(launcher_byte_tb_frames, VD_BYTE_PAIRS)
+#undef VD_X
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + kTb + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + kTb + kPun + C, M, 16>;
+VD_BYTE_TABLE(launcher_byte_punct_tb_frames, VD_BYTE_PUN_PAIRS)
+#undef VD_X
+#undef VD_BYTE_TABLE
+// the byte twin of the family (pun, tb)
+template <class L>
+typename L::fn launcher_byte(bool pun, bool tb, int ch, int me, bool o16)
+{
+    return tb && pun ? launcher_byte_punct_tb_frames<L>(ch, me, o16)
+           : tb      ? launcher_byte_tb_frames<L>(ch, me, o16)
+           : pun     ? launcher_byte_punct_frames<L>(ch, me, o16)
+                     : launcher_byte_frames<L>(ch, me, o16);
+}
+
 // ---------------------------------------------------------------- the knobs (read once, at vd_create)
 struct Knobs {
     int split = 1;    // segment launches: 0 none (VD_NO_SPLIT=1), 1 pieces, 2 thirds, 3 sevenths (VD_SPLIT=...)
@@ -324,12 +366,15 @@ inline constexpr const char* kCoreNames[3] = {"B32", "B16", "F16"};
 // vd_decoder_kernel_name: the kernel and launch form of one planned launch; input: 0 packed words, 1 float
 // channel values (LLR), 2 punctured float values (PUN), 3 frames of float values (FRM; a plan of plan_frames),
 // 4 punctured frames (FRM+PUN; a plan of plan_frames), 5 tail-biting frames (FRM+TB; a plan of plan_frames),
-// 6 punctured tail-biting frames (FRM+TB+PUN; a plan of plan_frames)
+// 6 punctured tail-biting frames (FRM+TB+PUN; a plan of plan_frames), 7 .. 10 the int8 twins of 3 .. 6 (FRM+I8+...)
 inline std::string plan_name(const LaunchPlan& p, int o, int input)
 {
     if (!p.launches) return "-";
-    const std::string args = std::string(input == 6 ? "FRM+TB+PUN+" : input == 5 ? "FRM+TB+" : input == 4 ? "FRM+PUN+" :
-                                         input == 3 ? "FRM+" : input == 2 ? "PUN+" : input ? "LLR+" : "") +
+    const bool i8 = input >= 7 && input <= 10;
+    if (i8) input -= 4;  // the float twin's name with I8+ after FRM+
+    const std::string fam = input == 6 ? "TB+PUN+" : input == 5 ? "TB+" : input == 4 ? "PUN+" : "";
+    const std::string args = std::string(input >= 3 && input <= 6 ? "FRM+" + std::string(i8 ? "I8+" : "") + fam :
+                                         input == 2 ? "PUN+" : input ? "LLR+" : "") +
                              kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," + (out_of(o) ? "O16" : "O32") + ">";
     if (input == 3 || input == 4 || input == 5 || input == 6)
         return "vd_decode_tg<" + args + " one frame per wave, " + (ch_of(o) == SOFT16 ? "int32 tagged patterns" : "fp32 tagged core") +

@@ -49,12 +49,16 @@ EXPORTS = ["vd_options_valid", "vd_input_size", "vd_message_len", "vd_output_siz
            "vd_decoder_kernel_name", "vd_punctured_len", "vd_run_device_punct", "vd_run_device_punct_batch",
            "vd_run_punct", "vd_frame_output_size", "vd_run_device_frames", "vd_run_frames",
            "vd_run_device_punct_frames", "vd_run_punct_frames", "vd_run_device_tb_frames", "vd_run_tb_frames",
-           "vd_run_device_punct_tb_frames", "vd_run_punct_tb_frames", "vd_set_frame_part_bits", "vd_frame_part_bits"]
+           "vd_run_device_punct_tb_frames", "vd_run_punct_tb_frames", "vd_set_frame_part_bits", "vd_frame_part_bits",
+           "vd_run_device_byte_frames", "vd_run_byte_frames"]
 
 # puncture patterns (period, keep0, keep1): bit i of keep0 / keep1 = the first (0171) / second (0133) encoder
 # output of the stages t with t % period == i is transmitted.  Any valid masks decode (and equal the rate-1/2
 # decode of the depunctured stream); these three are the ones the fixed decode window is long enough for
 # (DESIGN.md "Punctured streams")
+# the kind of an int8 frame launch (vd_capi.h VD_FRAMES_*)
+FRAMES_OPEN, FRAMES_TERMINATED, FRAMES_TAILBITING = 0, 1, 2
+
 PUNCTURE = {"1/2": (1, 1, 1), "2/3": (2, 0b01, 0b11), "3/4": (3, 0b101, 0b011)}
 
 
@@ -118,6 +122,9 @@ def lib():
            "vd_run_device_punct_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, i, ctypes.c_uint32, ctypes.c_uint32, vp], None),
            "vd_run_punct_tb_frames": ([vp, vp, sz, vp, sz, vp, sz, i, f, i, ctypes.c_uint32, ctypes.c_uint32,
                                        ctypes.POINTER(f)], None),
+           "vd_run_device_byte_frames": ([vp, vp, sz, vp, sz, vp, sz, i, i, f, i, ctypes.c_uint32, ctypes.c_uint32, vp], None),
+           "vd_run_byte_frames": ([vp, vp, sz, vp, sz, vp, sz, i, i, f, i, ctypes.c_uint32, ctypes.c_uint32,
+                                   ctypes.POINTER(f)], None),
            "vd_set_frame_part_bits": ([vp, sz], None), "vd_frame_part_bits": ([vp, ctypes.POINTER(sz)], None),
            "vd_kernel_name": ([i], ctypes.c_char_p),
            "vd_decoder_kernel_name": ([vp, sz, i, i], ctypes.c_char_p)}
@@ -268,7 +275,8 @@ class ViterbiCUDA:
         (vd_decoder_kernel_name: follows VD_NO_PK / VD_PK_SPLIT / VD_NO_SPLIT as read at creation); llr: False /
         0 packed input, True / 1 float channel values, 2 punctured float values, 3 a frame launch (inputNum =
         maxFrameBits, nbatch = nframes), 4 a launch of punctured frames (likewise), 5 a launch of tail-biting
-        frames (likewise), 6 a launch of punctured tail-biting frames (likewise; "-" on a HARD decoder)"""
+        frames (likewise), 6 a launch of punctured tail-biting frames (likewise; "-" on a HARD decoder), 7 .. 10 the
+        int8 twins of 3 .. 6 (run_device_byte_frames; "-" where that call is refused)"""
         return lib().vd_decoder_kernel_name(self._h, inputNum, nbatch, int(llr)).decode()
 
     def set_guard_check(self, enable=True):
@@ -517,6 +525,53 @@ class ViterbiCUDA:
         _check(lib().vd_run_device_punct_tb_frames(self._h, ctypes.c_void_p(rx_ptr), rx_stride, ctypes.c_void_p(output_ptr),
                                                    output_stride, ctypes.c_void_p(frame_bits_ptr) if frame_bits_ptr else None,
                                                    maxFrameBits, nframes, scale, *pattern, ctypes.c_void_p(stream)))
+
+    # ---- int8 frames: the four families above on int8 channel values, byte-wide loads (vd_capi.h "int8 frames") ----
+    def run_byte_frames(self, q_h, kind, pattern=(1, 1, 1), maxFrameBits=None, scale=1.0, frame_bits=None):
+        """Blocking decode of nframes frames of int8 channel values in one launch.  q_h: int8 array [nframes, L], row f
+        starts with frame f's kept values in mother order, one byte each (the row pitch is the stride); kind:
+        FRAMES_OPEN, FRAMES_TERMINATED or FRAMES_TAILBITING; pattern = (period, keep0, keep1), (1, 1, 1) for
+        unpunctured frames (then L must be even, and maxFrameBits defaults to L // 2; with any other pattern
+        maxFrameBits must be given and L >= punctured_len(pattern, 2 * maxFrameBits)); frame_bits: the stages of each
+        frame, as in run_frames.  Frame f equals, word for word, the float family's decode (run_frames,
+        run_punct_frames, run_tb_frames, run_punct_tb_frames) of q_h.astype(float32) with the same scale.  HARD (not
+        open, not punctured), SOFT4 and SOFT8 decoders; SOFT16 and FP32: VD_ERR_OPTIONS.  Returns (out, ms) shaped as
+        run_frames does."""
+        q_h = np.ascontiguousarray(q_h, dtype=np.int8)
+        if q_h.ndim != 2:
+            raise VitdecError("run_byte_frames: q_h must be [nframes, L]")
+        if maxFrameBits is None:
+            if tuple(pattern) != (1, 1, 1):
+                raise VitdecError("run_byte_frames: maxFrameBits must be given with a puncture pattern")
+            maxFrameBits = q_h.shape[1] // 2
+        need = punctured_len(pattern, 2 * maxFrameBits)  # (0 too for an invalid pattern, which the call below reports)
+        if q_h.shape[1] < need:
+            raise VitdecError(f"run_byte_frames: rows of {q_h.shape[1]} values, punctured_len{tuple(pattern)} of "
+                              f"{2 * maxFrameBits} is {need}")
+        nframes = q_h.shape[0]
+        row = frame_output_size(self.options, maxFrameBits)
+        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
+        fb = None
+        if frame_bits is not None:
+            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
+            if fb.shape != (nframes,):
+                raise VitdecError("run_byte_frames: frame_bits must hold one length per frame")
+        ms = ctypes.c_float(0.0)
+        _check(lib().vd_run_byte_frames(self._h, q_h.ctypes.data, q_h.shape[1], out.ctypes.data, row,
+                                        fb.ctypes.data if fb is not None else None, maxFrameBits, nframes, kind, scale,
+                                        *pattern, ctypes.byref(ms)))
+        return out, ms.value
+
+    def run_device_byte_frames(self, q_ptr, q_stride, output_ptr, output_stride, maxFrameBits, nframes, kind,
+                               pattern=(1, 1, 1), scale=1.0, frame_bits_ptr=0, stream=0):
+        """Async decode of nframes frames of int8 channel values in one launch (vd_run_device_byte_frames): frame f
+        reads its punctured_len(pattern, 2 S_f) bytes at q_ptr + f * q_stride bytes (pattern (1, 1, 1): both multiples
+        of 2; else any address and stride) and writes 4 * ceil(S_f / 32) bytes at output_ptr + f * output_stride; S_f =
+        min(lengths[f], maxFrameBits) stages with frame_bits_ptr a device array of uint32 lengths, or maxFrameBits
+        when it is 0."""
+        _check(lib().vd_run_device_byte_frames(self._h, ctypes.c_void_p(q_ptr), q_stride, ctypes.c_void_p(output_ptr),
+                                               output_stride, ctypes.c_void_p(frame_bits_ptr) if frame_bits_ptr else None,
+                                               maxFrameBits, nframes, kind, scale, *pattern, ctypes.c_void_p(stream)))
 
 
 class PinnedArray:

@@ -181,8 +181,9 @@ int vd_run_punct(vd_decoder* dec, const float* rx_h, void* output_h, size_t inpu
  * [1, 2^20], nframes < 1, scale not finite and > 0, a misaligned pointer or stride, overlapping frames.
  * Punctured frames: vd_run_device_punct_frames below; tail-biting frames: vd_run_device_tb_frames below; punctured
  * tail-biting frames: vd_run_device_punct_tb_frames below.
- * Packed-word frames, frames longer than 2^20 stages and vd_decode_pk twins of the frame kernels are not
- * supported. */
+ * Frames of int8 channel values are supported: vd_run_device_byte_frames below, for all four families.  The
+ * reference's MSB-first packed words as frame input, int16 frames, frames longer than 2^20 stages and vd_decode_pk
+ * twins of the frame kernels are not. */
 
 /* bytes a frame of frameBits stages decodes to: 4 * ceil(frameBits / 32), for O_B32 and O_B16 alike */
 size_t vd_frame_output_size(int options, size_t frameBits);
@@ -305,7 +306,7 @@ int vd_run_punct_tb_frames(vd_decoder* dec, const float* rx_h, size_t rx_stride,
 /* ---- long frames in parts spread over many waves (new: a few long frames, e.g. one DVB or CCSDS burst, would
  *      otherwise occupy a few waves of a GPU that holds thousands) ----
  * A decoder carries a part length partBits: 0 (the default: one wave decodes a whole frame, everything above) or
- * a multiple of 96 in [96, 2^20].  All eight frame entry points above honour it; their signatures and argument
+ * a multiple of 96 in [96, 2^20].  All eight frame entry points above, and the two int8 ones below, honour it; their signatures and argument
  * rules do not change.  With Wp = partBits / 32, a frame of S stages, W = ceil(S / 32), has ceil(W / Wp) parts,
  * and part j holds w_j = min(Wp, W - j Wp) words.  Part j decodes, word for word, as the one-chunk decode
  * (inputNum = 2 (64 + 32 w_j), nchunks = 1, O_B16 policy 0) of stages [32 j Wp, 32 j Wp + 64 + 32 w_j) of the
@@ -325,6 +326,47 @@ int vd_run_punct_tb_frames(vd_decoder* dec, const float* rx_h, size_t rx_stride,
 /* VD_ERR_ARG unless partBits is 0 or a multiple of 96 in [96, 2^20] */
 int vd_set_frame_part_bits(vd_decoder* dec, size_t partBits);
 int vd_frame_part_bits(vd_decoder* dec, size_t* partBits);
+
+/* ---- int8 frames (new: the soft values a demapper delivers, e.g. 802.11, DVB, 802.16 or CCSDS int8 LLRs, decoded
+ *      as they are: no widening pass, no float buffer four times the size of the data) ----
+ * The four frame families above on frames of int8 channel values.  A frame of S stages under a pattern (period,
+ * keep0, keep1) holds vd_punctured_len(period, keep0, keep1, 2 S) int8 values: the kept values of its 2 S mother-code
+ * values in mother order (first encoder output first), one byte each, in plain memory order -- not the reference's
+ * MSB-first packed words.  The decode equals, word for word, the float entry point of the same family on the buffer
+ * (float)q, with the same scale, lengths and pattern and float strides of 4 x the byte strides:
+ *   kind                   pattern (1, 1, 1)                         any other valid pattern
+ *   VD_FRAMES_OPEN         vd_run_device_frames, terminated = 0      vd_run_device_punct_frames, terminated = 0
+ *   VD_FRAMES_TERMINATED   vd_run_device_frames, terminated = 1      vd_run_device_punct_frames, terminated = 1
+ *   VD_FRAMES_TAILBITING   vd_run_device_tb_frames                   vd_run_device_punct_tb_frames
+ * Everything those contracts say carries over: the pad value -65536 / scale, erasures as +0.0f, the pattern's phase
+ * restarting per frame and per wrap, S_f = min(frame_bits_d[f], maxFrameBits), S_f = 0 writing nothing, exactly the
+ * frame's bytes read and exactly its words written, and the decoder's part length (vd_set_frame_part_bits).  The
+ * values are multiplied by scale, rounded and saturated to the decoder's format like the floats they stand for
+ * (scale 1 on a SOFT8 decoder: the values themselves).  Only the loads differ from the float kernels: pattern
+ * (1, 1, 1) reads a stage's two values as one 16-bit access, so q_d and q_stride must be multiples of 2; any other
+ * pattern reads single bytes at any address and any stride.  output_stride is a multiple of 4.
+ * HARD, SOFT4 and SOFT8 decoders, every metric and output width.  VD_ERR_OPTIONS: a SOFT16 or FP32 decoder (an int8
+ * value carries nothing that a SOFT8 decoder does not use), and a HARD decoder with VD_FRAMES_OPEN or with a pattern
+ * other than (1, 1, 1), as in the float API.  VD_ERR_ARG: a kind outside 0 .. 2, an invalid pattern, maxFrameBits
+ * outside [1, 2^20], nframes < 1, a scale the float family rejects (finite and > 0; open and terminated frames also
+ * need -65536 / scale finite), a q_d or q_stride that is odd under (1, 1, 1), output_stride % 4, with nframes > 1 a
+ * q_stride < vd_punctured_len(period, keep0, keep1, 2 * maxFrameBits) or an output_stride <
+ * vd_frame_output_size(maxFrameBits), and the workgroup limit of frames in parts. */
+#define VD_FRAMES_OPEN        0
+#define VD_FRAMES_TERMINATED  1
+#define VD_FRAMES_TAILBITING  2
+
+/* nframes frames of int8 channel values in one launch, under the rules of vd_run_device_frames (asynchronous, no
+ * allocation, capturable, the stream on the decoder's device) */
+int vd_run_device_byte_frames(vd_decoder* dec, const int8_t* q_d, size_t q_stride, void* output_d, size_t output_stride,
+                              const uint32_t* frame_bits_d /* device, or NULL: every frame has maxFrameBits */,
+                              size_t maxFrameBits, int nframes, int kind, float scale, int period, uint32_t keep0,
+                              uint32_t keep1, void* stream);
+/* Blocking host-to-host variant over host buffers of the same layout (H2D, the launch, D2H); the output bytes
+ * no frame writes keep their values.  kernel_ms as in vd_run. */
+int vd_run_byte_frames(vd_decoder* dec, const int8_t* q_h, size_t q_stride, void* output_h, size_t output_stride,
+                       const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int kind, float scale, int period,
+                       uint32_t keep0, uint32_t keep1, float* kernel_ms);
 
 /* ---- the reference harness's channel source (RandBitGen | ConvolutionalEncoder | AddNoise |
  *      SoftDecisionPacker, viterbiDF.h:20-167), host and GPU ---- */
@@ -381,7 +423,9 @@ const char* vd_kernel_name(int options);
  * inputNum and nbatch as for llr 3, "-" on a HARD decoder; llr 5: the launch of vd_run_device_tb_frames
  * (vd_decode_tg<FRM+TB+...>), inputNum and nbatch as for llr 3; llr 6: the launch of
  * vd_run_device_punct_tb_frames (vd_decode_tg<FRM+TB+PUN+...>), inputNum and nbatch as for llr 3, "-" on a HARD
- * decoder; valid until the thread's next call */
+ * decoder; llr 7 .. 10: the launch of vd_run_device_byte_frames that is the int8 twin of llr 3 .. 6 (the twin's name
+ * with I8+ after FRM+, e.g. vd_decode_tg<FRM+I8+TB+PUN+...>), "-" where that call returns VD_ERR_OPTIONS (SOFT16 and
+ * FP32 decoders; llr 8 and 10 on a HARD decoder); valid until the thread's next call */
 const char* vd_decoder_kernel_name(vd_decoder* dec, size_t inputNum, int nbatch, int llr);
 /* build record: "<16 hex digits of the SHA-256 of the concatenated sources> <their paths, relative to the
  * package directory>"; the Python binding refuses a library whose sources have changed since (stale build) */
