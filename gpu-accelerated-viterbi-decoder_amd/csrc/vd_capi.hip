@@ -98,6 +98,11 @@ struct vd_decoder {
     Knobs knobs;                // VD_NO_SPLIT / VD_SPLIT / VD_NO_PK / VD_PK_SPLIT / VD_PK_TAIL as read at vd_create
     uint32_t* check = nullptr;  // LDS guard violation counter (vd_set_guard_check), null = off
     uint32_t partBits = 0;      // frame launches decode frames in parts of this many stages (vd_set_frame_part_bits), 0 = whole
+    // mixed frames (vd_set_frame_patterns): the pattern table, its host copy and its device records (allocated by the
+    // first setter call, the only allocation of the mixed launches; the kernels read it when they run)
+    MixRecord mixTab[kMixMaxPatterns];
+    int mixN = 0;
+    void* mixTab_d = nullptr;
 };
 
 // a device buffer of at least need bytes (contents not kept)
@@ -265,7 +270,9 @@ const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, i
     if (llr == 6 && ch_of(d->options) == HARD) return "-";  // ... nor punctured tail-biting HARD frames
     // the int8 twins of 3 .. 6 (7 .. 10): HARD, SOFT4 and SOFT8 decoders, the punctured ones not on HARD
     if (llr >= 7 && llr <= 10 && (ch_of(d->options) > SOFT8 || (ch_of(d->options) == HARD && (llr == 8 || llr == 10)))) return "-";
-    if (llr >= 3 && llr <= 10) {  // a frame launch (4: of punctured, 5: of tail-biting, 6: of punctured tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
+    // mixed frames (11, 12; their int8 twins 13, 14): punctured kernels, so not on HARD; int8 on SOFT4 and SOFT8 only
+    if (llr >= 11 && llr <= 14 && (ch_of(d->options) == HARD || (llr >= 13 && ch_of(d->options) > SOFT8))) return "-";
+    if (llr >= 3 && llr <= 14) {  // a frame launch (4: of punctured, 5: of tail-biting, 6: of punctured tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
         if (inputNum < 1 || inputNum > kFrmMaxBits) return "-";
         if (frame_parts_error(inputNum, nbatch, d->partBits)) return "-";  // (more workgroups than a launch can have)
         name = plan_name(plan_frames(d->options, (uint64_t)nbatch, frame_parts((uint32_t)inputNum, frame_part_words(d->partBits))),
@@ -335,6 +342,7 @@ int vd_destroy(vd_decoder* d)
     if (d->ev1) (void)hipEventDestroy(d->ev1);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->check) (void)hipFree(d->check);
+    if (d->mixTab_d) (void)hipFree(d->mixTab_d);
     delete d;
     return VD_OK;
 }
@@ -591,19 +599,28 @@ static int frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, 
     return VD_OK;
 }
 
+// a mixed launch's per-frame arrays (device; null: pattern 0 / frames at f strides)
+struct MixArgs {
+    const uint8_t* rate_d;
+    const uint64_t* off_d;
+};
+
 // the one launch of checked arguments; pun: the frames hold the kept values of punctured frames, tb: the frames
 // are tail-biting (no pad: terminated means nothing), both: punctured tail-biting frames (vd_frames.h)
 // i8: the frames hold int8 values, llr_stride counts their bytes (vd_frames.h "int8 frames")
+// mix: frames of mixed code rates under the decoder's pattern table (vd_frames.h "mixed frames"; pun is then null)
 static int launch_frames_checked(vd_decoder* d, const void* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
                                  const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
-                                 hipStream_t s, const Punct* pun = nullptr, bool tb = false, bool i8 = false)
+                                 hipStream_t s, const Punct* pun = nullptr, bool tb = false, bool i8 = false,
+                                 const MixArgs* mix = nullptr)
 {
     const int options = d->options;
     // the decoder's part length, read here, on the host: a captured graph keeps the value it was captured with
     const uint32_t partBits = d->partBits;
     if (const char* why = frame_parts_error(maxFrameBits, nframes, partBits)) return fail(VD_ERR_ARG, why);
     const LaunchPlan p = plan_frames(options, (uint64_t)nframes, frame_parts((uint32_t)maxFrameBits, frame_part_words(partBits)));
-    launch_fn f = i8 ? launcher_byte<Launch>(pun != nullptr, tb, ch_of(options), met_of(options), out_of(options) == 1)
+    launch_fn f = mix ? launcher_mixed<Launch>(i8, tb, ch_of(options), met_of(options), out_of(options) == 1)
+                  : i8 ? launcher_byte<Launch>(pun != nullptr, tb, ch_of(options), met_of(options), out_of(options) == 1)
                   : tb && pun ? launcher_punct_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                   : tb  ? launcher_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
                   : pun ? launcher_punct_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
@@ -630,6 +647,12 @@ static int launch_frames_checked(vd_decoder* d, const void* llr_d, size_t llr_st
     g.frmTerm = terminated ? 1u : 0u;
     if (!tb) frame_pad(scale, &g.frmPad);  // (checked by the caller)
     if (pun) g.pun = *pun;
+    if (mix) {  // the table as a device pointer: read by the kernel when it runs
+        g.mixPat = (const uint32_t*)d->mixTab_d;
+        g.mixN = (uint32_t)d->mixN;
+        g.mixRate = mix->rate_d;
+        g.mixOff = mix->off_d;
+    }
     if (p.parts > 1) {  // (one part: the grid and the arguments of a whole-frame launch)
         g.frmPartW = frame_part_words(partBits);
         g.frmPartG = frame_part_groups(p.parts);
@@ -944,6 +967,149 @@ int vd_run_byte_frames(vd_decoder* d, const int8_t* q_h, size_t q_stride, void* 
     VD_HIP(hipStreamSynchronize(d->stream));
     if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
     return VD_OK;
+}
+
+// ---- mixed frames (vd_frames.h "mixed frames"; vd_decode_tg<FRM+MIX+...>, one pattern and one place per frame) ----
+int vd_set_frame_patterns(vd_decoder* d, const uint32_t* triples, int n)
+{
+    if (!d) return fail(VD_ERR_ARG, "null argument");
+    if (const char* why = mixed_table_error(triples, n)) return fail(VD_ERR_ARG, why);
+    MixRecord tab[kMixMaxPatterns] = {};  // (the records past n: period 0, never read behind mixN)
+    for (int i = 0; i < n; i++) tab[i] = mix_record((int)triples[3 * i], triples[3 * i + 1], triples[3 * i + 2]);
+    VD_HIP(hipSetDevice(d->device));
+    if (!d->mixTab_d) VD_HIP(hipMalloc(&d->mixTab_d, sizeof(d->mixTab)));
+    // blocking: hipMemcpy from pageable memory returns after the copy, so the table is in place when the call returns
+    // (no launch of this decoder may be in flight: nothing else to wait for)
+    VD_HIP(hipMemcpy(d->mixTab_d, tab, sizeof(tab), hipMemcpyHostToDevice));
+    memcpy(d->mixTab, tab, sizeof(tab));
+    d->mixN = n;
+    return VD_OK;
+}
+int vd_frame_patterns(vd_decoder* d, uint32_t* triples, int* n)
+{
+    if (!d || !n) return fail(VD_ERR_ARG, "null argument");
+    *n = d->mixN;
+    for (int i = 0; triples && i < d->mixN; i++) {
+        triples[3 * i] = d->mixTab[i].pn.period;
+        triples[3 * i + 1] = d->mixTab[i].pn.keep0;
+        triples[3 * i + 2] = d->mixTab[i].pn.keep1;
+    }
+    return VD_OK;
+}
+
+// the argument checks of a mixed frame decode: VD_ERR_ARG / VD_ERR_OPTIONS
+static int mixed_frames_args(const vd_decoder* d, const void* rx, size_t rx_stride, bool offsets, const void* output,
+                             size_t output_stride, size_t maxFrameBits, int nframes, int kind, float scale, bool i8, bool device)
+{
+    if (!d || !rx || !output) return fail(VD_ERR_ARG, "null argument");
+    const int ch = ch_of(d->options);
+    if (ch == HARD)
+        return fail(VD_ERR_OPTIONS, "mixed frames on a HARD decoder: a punctured value must decode as code 0 = value 0, and "
+                                    "HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");
+    if (i8 && ch != SOFT4 && ch != SOFT8)
+        return fail(VD_ERR_OPTIONS, "int8 frames on a SOFT16 or FP32 decoder: an int8 value carries nothing that a SOFT8 "
+                                    "decoder does not use; use SOFT4 or SOFT8");
+    if (const char* why = mixed_args_error(device ? (uint64_t)(uintptr_t)rx : 0, rx_stride, offsets, output_stride, maxFrameBits,
+                                           nframes, kind, scale, d->mixTab, d->mixN, i8 ? 1u : 4u, d->partBits))
+        return fail(VD_ERR_ARG, why);
+    return VD_OK;
+}
+
+static int run_device_mixed(vd_decoder* d, const void* rx_d, size_t rx_stride, const uint64_t* rx_offsets_d, void* output_d,
+                            size_t output_stride, const uint32_t* frame_bits_d, const uint8_t* rate_d, size_t maxFrameBits,
+                            int nframes, int kind, float scale, hipStream_t s, bool i8)
+{
+    int rc = mixed_frames_args(d, rx_d, rx_stride, rx_offsets_d != nullptr, output_d, output_stride, maxFrameBits, nframes, kind,
+                               scale, i8, true);
+    if (rc != VD_OK) return rc;
+    const MixArgs mix = {rate_d, rx_offsets_d};
+    return launch_frames_checked(d, rx_d, rx_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes,
+                                 kind == kByteFramesTerminated, scale, s, nullptr, kind == kByteFramesTailbiting, i8, &mix);
+}
+
+int vd_run_device_mixed_frames(vd_decoder* d, const float* rx_d, size_t rx_stride, const uint64_t* rx_offsets_d, void* output_d,
+                               size_t output_stride, const uint32_t* frame_bits_d, const uint8_t* rate_d, size_t maxFrameBits,
+                               int nframes, int kind, float scale, void* stream)
+{
+    return run_device_mixed(d, rx_d, rx_stride, rx_offsets_d, output_d, output_stride, frame_bits_d, rate_d, maxFrameBits, nframes,
+                            kind, scale, (hipStream_t)stream, false);
+}
+int vd_run_device_byte_mixed_frames(vd_decoder* d, const int8_t* q_d, size_t q_stride, const uint64_t* q_offsets_d, void* output_d,
+                                    size_t output_stride, const uint32_t* frame_bits_d, const uint8_t* rate_d, size_t maxFrameBits,
+                                    int nframes, int kind, float scale, void* stream)
+{
+    return run_device_mixed(d, q_d, q_stride, q_offsets_d, output_d, output_stride, frame_bits_d, rate_d, maxFrameBits, nframes,
+                            kind, scale, (hipStream_t)stream, true);
+}
+
+// the host buffers laid out like the device ones (vd_run_frames).  Without offsets the last frame's part ends with the
+// received values of a maxFrameBits frame under the table's densest pattern; with offsets the buffer holds rx_total
+// values and every frame must lie inside it (checked here, where the arrays are at hand).  The staging buffers are the
+// decoder's: the offsets, the lengths and the rate indices ride behind the values.
+static int run_mixed(vd_decoder* d, const void* rx_h, size_t rx_stride, const uint64_t* rx_offsets_h, size_t rx_total,
+                     void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h, size_t maxFrameBits,
+                     int nframes, int kind, float scale, float* kernel_ms, bool i8)
+{
+    int rc = mixed_frames_args(d, rx_h, rx_stride, rx_offsets_h != nullptr, output_h, output_stride, maxFrameBits, nframes, kind,
+                               scale, i8, false);
+    if (rc != VD_OK) return rc;
+    const size_t vb = i8 ? 1 : 4;
+    if (rx_offsets_h) {
+        if (rx_total > ((size_t)1 << 40)) return fail(VD_ERR_ARG, "rx_total above 2^40 values");
+        for (int f = 0; f < nframes; f++) {
+            const uint32_t ri = rate_h ? rate_h[f] : 0u;
+            const uint32_t S = frame_bits_h && frame_bits_h[f] < maxFrameBits ? frame_bits_h[f] : (uint32_t)maxFrameBits;
+            if (ri >= (uint32_t)d->mixN || S == 0) continue;  // (reads nothing)
+            if (!mixed_frame_inside(rx_offsets_h[f], pfrm_bytes<1>(d->mixTab[ri].pn, S), rx_total))
+                return fail(VD_ERR_ARG, "frame " + std::to_string(f) + " does not lie inside the rx_total values of the buffer");
+        }
+    }
+    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
+    const size_t lastB = i8 ? mix_max_bytes<1>(d->mixTab, d->mixN, (uint32_t)maxFrameBits)
+                            : mix_max_bytes<4>(d->mixTab, d->mixN, (uint32_t)maxFrameBits);
+    const size_t inB = rx_offsets_h ? rx_total * vb : (size_t)(nframes - 1) * rx_stride + lastB;
+    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
+    const size_t offOff = (inB + 15) & ~(size_t)15, offB = rx_offsets_h ? (size_t)nframes * 8 : 0;
+    const size_t lenOff = offOff + offB, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
+    const size_t rateOff = lenOff + lenB, rateB = rate_h ? (size_t)nframes : 0;
+    VD_HIP(hipSetDevice(d->device));
+    rc = grow(d->llr_d, d->cap_llr, rateOff + rateB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
+    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
+    if (rc != VD_OK) return rc;
+    uint64_t* const off_d = rx_offsets_h ? (uint64_t*)((char*)d->llr_d + offOff) : nullptr;
+    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
+    uint8_t* const rate_d = rate_h ? (uint8_t*)d->llr_d + rateOff : nullptr;
+    if (inB) VD_HIP(hipMemcpyAsync(d->llr_d, rx_h, inB, hipMemcpyHostToDevice, d->stream));
+    if (off_d) VD_HIP(hipMemcpyAsync(off_d, rx_offsets_h, offB, hipMemcpyHostToDevice, d->stream));
+    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
+    if (rate_d) VD_HIP(hipMemcpyAsync(rate_d, rate_h, rateB, hipMemcpyHostToDevice, d->stream));
+    // the words no frame writes (between the frames, of short, empty and out-of-table frames) keep the caller's values
+    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
+    VD_HIP(hipEventRecord(d->ev0, d->stream));
+    const MixArgs mix = {rate_d, off_d};
+    rc = launch_frames_checked(d, d->llr_d, rx_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes,
+                               kind == kByteFramesTerminated, scale, d->stream, nullptr, kind == kByteFramesTailbiting, i8, &mix);
+    if (rc != VD_OK) return rc;
+    VD_HIP(hipEventRecord(d->ev1, d->stream));
+    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
+    VD_HIP(hipStreamSynchronize(d->stream));
+    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    return VD_OK;
+}
+
+int vd_run_mixed_frames(vd_decoder* d, const float* rx_h, size_t rx_stride, const uint64_t* rx_offsets_h, size_t rx_total,
+                        void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h,
+                        size_t maxFrameBits, int nframes, int kind, float scale, float* kernel_ms)
+{
+    return run_mixed(d, rx_h, rx_stride, rx_offsets_h, rx_total, output_h, output_stride, frame_bits_h, rate_h, maxFrameBits,
+                     nframes, kind, scale, kernel_ms, false);
+}
+int vd_run_byte_mixed_frames(vd_decoder* d, const int8_t* q_h, size_t q_stride, const uint64_t* q_offsets_h, size_t q_total,
+                             void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h,
+                             size_t maxFrameBits, int nframes, int kind, float scale, float* kernel_ms)
+{
+    return run_mixed(d, q_h, q_stride, q_offsets_h, q_total, output_h, output_stride, frame_bits_h, rate_h, maxFrameBits, nframes,
+                     kind, scale, kernel_ms, true);
 }
 
 void* vd_host_alloc(size_t bytes)

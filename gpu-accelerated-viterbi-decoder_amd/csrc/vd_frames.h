@@ -490,4 +490,83 @@ inline const char* byte_frame_args_error(uint64_t q_addr, uint64_t q_stride, uin
     return frame_parts_error(maxFrameBits, nframes, partBits);
 }
 
+// ---------------------------------------------------------------- mixed frames (channel ids kMix + a punctured frame id)
+// One launch of frames at several code rates: frame f decodes under pattern rate[f] of a table of up to kMixMaxPatterns
+// patterns the decoder holds on the device, and may start at its own value index off[f] of the received buffer instead
+// of at f strides.  The table is an array of 32-byte records, a record the Punct of punct_make (6 dwords) and 2 dwords
+// of padding: a wave reads its record once at set-up (index out of the table: the wave returns before any load of
+// received values) and from there on the kernel is the punctured family's, with the wave's own pattern where the
+// uniform launch has Geom::pun.  (1, 1, 1) is a legal entry and takes the same punctured path (single-value loads: no
+// 8-byte or 2-byte alignment rule), whose words equal the unpunctured family's.  An offset counts values (floats, or
+// bytes for int8), so every offset is aligned by construction; the frame's resource covers its pfrm_bytes from there,
+// exactly as it does at f strides.  tests/cxx/mixed_frames_check.cpp checks the helpers below against a plain
+// enumeration.
+constexpr int kMixMaxPatterns = 16;
+constexpr uint32_t kMixRecordDwords = 8;  // a record's stride in the device table
+struct MixRecord {
+    Punct pn;
+    uint32_t pad[2] = {0u, 0u};
+};
+static_assert(sizeof(MixRecord) == 4 * kMixRecordDwords && sizeof(Punct) == 24, "the device table's record layout");
+// the record of a valid pattern
+inline MixRecord mix_record(int period, uint32_t keep0, uint32_t keep1)
+{
+    MixRecord r;
+    r.pn = punct_make(period, keep0, keep1);
+    return r;
+}
+// vd_set_frame_patterns' checks of n (period, keep0, keep1) triples (VD_ERR_ARG): the message, or null
+inline const char* mixed_table_error(const uint32_t* triples, int n)
+{
+    if (n < 0 || n > kMixMaxPatterns) return "n must be in [0, 16]";
+    if (n > 0 && !triples) return "null triples with n > 0";
+    for (int i = 0; i < n; i++) {
+        const uint32_t period = triples[3 * i];
+        if (period > (uint32_t)kPunctMaxPeriod || !punct_valid((int)period, triples[3 * i + 1], triples[3 * i + 2]))
+            return "invalid puncture pattern in the table: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
+    }
+    return nullptr;
+}
+// the received bytes of the longest frame of S stages over a table of n records
+template <uint32_t VB = 4>
+inline uint32_t mix_max_bytes(const MixRecord* table, int n, uint32_t S)
+{
+    uint32_t m = 0;
+    for (int i = 0; i < n; i++) {
+        const uint32_t b = pfrm_bytes<VB>(table[i].pn, S);
+        m = b > m ? b : m;
+    }
+    return m;
+}
+// The argument checks of vd_run_device_mixed_frames (vb = 4) and vd_run_device_byte_mixed_frames (vb = 1), all
+// VD_ERR_ARG: the message, or null when the arguments are good.  rx_addr: the address the offsets or strides count
+// from; offsets: the launch has per-frame offsets (rx_stride is then ignored); table, n: the decoder's patterns.
+inline const char* mixed_args_error(uint64_t rx_addr, uint64_t rx_stride, bool offsets, uint64_t output_stride, uint64_t maxFrameBits,
+                                    int nframes, int kind, float scale, const MixRecord* table, int n, uint32_t vb, uint64_t partBits)
+{
+    float pad;
+    if (n < 1 || n > kMixMaxPatterns || !table) return "the decoder's pattern table is empty: call vd_set_frame_patterns first";
+    if (kind != kByteFramesOpen && kind != kByteFramesTerminated && kind != kByteFramesTailbiting)
+        return "kind must be VD_FRAMES_OPEN, VD_FRAMES_TERMINATED or VD_FRAMES_TAILBITING";
+    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
+    if (nframes < 1) return "nframes must be >= 1";
+    if (kind == kByteFramesTailbiting) {
+        if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
+    } else if (!frame_pad(scale, &pad)) {
+        return "scale must be finite and > 0 (and -65536 / scale finite)";
+    }
+    if (vb == 4 && (rx_addr & 3)) return "rx_d must be 4-byte aligned";
+    if (vb == 4 && !offsets && (rx_stride & 3)) return "rx_stride must be a multiple of 4 bytes";
+    if (output_stride & 3) return "output_stride must be a multiple of 4 bytes";
+    if (nframes > 1 && !offsets &&
+        rx_stride < (vb == 4 ? mix_max_bytes<4>(table, n, (uint32_t)maxFrameBits) : mix_max_bytes<1>(table, n, (uint32_t)maxFrameBits)))
+        return "rx_stride smaller than the received bytes of a maxFrameBits frame under the table's densest pattern: frames would overlap";
+    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
+        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
+    return frame_parts_error(maxFrameBits, nframes, partBits);
+}
+// The blocking host variants know every frame's place: frame f (S stages, pattern index rate, out-of-table or S = 0:
+// nothing read) must lie inside the total values of the buffer.  first .. first + count: the values it reads.
+inline bool mixed_frame_inside(uint64_t first, uint64_t count, uint64_t total) { return count <= total && first <= total - count; }
+
 }  // namespace vd

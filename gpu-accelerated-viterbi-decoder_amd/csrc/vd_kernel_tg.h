@@ -54,6 +54,10 @@ constexpr int kTb = 32;
 // kI8 + one of the four frame ids above (HARD, SOFT4, SOFT8) = the same frames held as int8 channel values, one
 // byte each: byte-wide loads widened to the float pair of the family's float kernel (TgInI8, "int8 frames" below)
 constexpr int kI8 = 64;
+// kMix + one of the punctured frame ids (kFrm + kPun, kFrm + kTb + kPun, and their kI8 twins) = frames of mixed code
+// rates: each wave takes its frame's own pattern from a device table and its frame's own place in the received
+// buffer (TgInMix, "mixed frames" below)
+constexpr int kMix = 128;
 
 template <int CH>
 struct TgFmt {
@@ -879,6 +883,32 @@ __device__ __forceinline__ float2 tg_i8_widen(float2 r)
     return make_float2(x, y);
 }
 
+// ---------------------------------------------------------------- mixed frames (vd_frames.h "mixed frames")
+// kMix + a punctured frame id (float or int8) = the family's frames at mixed code rates in one launch.  Only the wave's
+// set-up differs from the twin without kMix: right after its frame and length the wave reads its frame's rate index (a
+// byte), returns if the index lies outside the table, and reads the index's 32-byte record -- the six dwords of a Punct
+// -- into scalar registers (uniform address, read before the kernel's first store: the compiler takes the scalar
+// unit's loads, and readfirstlane keeps the values scalar wherever it does not).  That local Punct stands where the
+// twin has Geom::pun: the frame's received bytes, the first group's and every later group's index map.  With per-frame
+// offsets (Geom::mixOff) the frame's 64-bit scalar base is the buffer's plus off[f] values instead of f strides; the
+// frame's resource bounds every load as in the twin.  Nothing after the loads changes, and no register lives longer
+// than in the twin: the record replaces six kernel-argument dwords, the rate index and the offset die at set-up.
+template <class FAM>
+struct TgInMix : FAM {
+    static constexpr bool MIX = true;
+};
+#define VD_TG_MIX(ID) template <> struct TgIn<kMix + (ID)> : TgInMix<TgIn<(ID)>> {};
+VD_TG_MIX(kFrm + kPun + SOFT4) VD_TG_MIX(kFrm + kPun + SOFT8) VD_TG_MIX(kFrm + kPun + SOFT16) VD_TG_MIX(kFrm + kPun + FP32)
+VD_TG_MIX(kFrm + kTb + kPun + SOFT4) VD_TG_MIX(kFrm + kTb + kPun + SOFT8) VD_TG_MIX(kFrm + kTb + kPun + SOFT16)
+VD_TG_MIX(kFrm + kTb + kPun + FP32)
+VD_TG_MIX(kI8 + kFrm + kPun + SOFT4) VD_TG_MIX(kI8 + kFrm + kPun + SOFT8)
+VD_TG_MIX(kI8 + kFrm + kTb + kPun + SOFT4) VD_TG_MIX(kI8 + kFrm + kTb + kPun + SOFT8)
+#undef VD_TG_MIX
+template <class T, class = void>
+struct HasMix : std::false_type {};
+template <class T>
+struct HasMix<T, std::void_t<decltype(T::MIX)>> : std::bool_constant<T::MIX> {};
+
 // ---------------------------------------------------------------- segment launches
 // A launch of 6400 chunks on 1024 SIMDs, one chunk per wave, puts 7 waves on a quarter of the SIMDs and
 // 6 on the rest, and the 7-wave SIMDs set the kernel time.  In a segment launch (Geom::seg) workgroup g
@@ -1020,9 +1050,40 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
     uint32_t pfrB = 0;                       // its received bytes (wave-uniform)
     constexpr bool I8 = HasI8<IN>::value;    // ... held as int8 values: byte-wide loads (tg_i8_widen)
     constexpr uint32_t VB = I8 ? 1 : 4;      // bytes of a channel value in the frame's buffer
-    if constexpr (PFR || PTB) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes<VB>(geo.pun, frmS));
+    // ... of mixed code rates ("mixed frames" above): the wave's own pattern, read from the table into scalar
+    // registers, stands for Geom::pun from here on; an index outside the table: nothing to decode
+    constexpr bool MIX = HasMix<IN>::value;
+    static_assert(!MIX || PFR || PTB, "mixed frames are punctured frames");
+    Punct mixPn;
+    if constexpr (MIX) {
+        const uint32_t ri = __builtin_amdgcn_readfirstlane(geo.mixRate ? (uint32_t)geo.mixRate[frmF] : 0u);
+        if (ri >= geo.mixN) return;
+        const uint32_t* const rec = geo.mixPat + kMixRecordDwords * ri;
+        mixPn.period = __builtin_amdgcn_readfirstlane(rec[0]);
+        mixPn.keep0 = __builtin_amdgcn_readfirstlane(rec[1]);
+        mixPn.keep1 = __builtin_amdgcn_readfirstlane(rec[2]);
+        mixPn.kp = __builtin_amdgcn_readfirstlane(rec[3]);
+        mixPn.recip = __builtin_amdgcn_readfirstlane(rec[4]);
+        mixPn.m16 = __builtin_amdgcn_readfirstlane(rec[5]);
+    }
+    const Punct& pun = [&]() -> const Punct& {
+        if constexpr (MIX) return mixPn;
+        else return geo.pun;
+    }();
+    if constexpr (PFR || PTB) pfrB = __builtin_amdgcn_readfirstlane(pfrm_bytes<VB>(pun, frmS));
     const uint32_t batch = FRM ? frmF : geo.nbatch > 1 && !split ? gchunk / geo.nchunks : 0u;
-    const void* const in = (const char*)in_all + batch * geo.inStride;
+    // (mixed frames with offsets: the frame starts at value off[f] of the buffer, a 64-bit scalar like f strides)
+    const uint64_t inOff = [&]() -> uint64_t {
+        if constexpr (MIX) {
+            if (geo.mixOff) {
+                const uint64_t o = geo.mixOff[frmF];
+                const uint32_t ol = __builtin_amdgcn_readfirstlane((uint32_t)o), oh = __builtin_amdgcn_readfirstlane((uint32_t)(o >> 32));
+                return ((uint64_t)oh << 32 | ol) * VB;
+            }
+        }
+        return batch * geo.inStride;
+    }();
+    const void* const in = (const char*)in_all + inOff;
     void* const out = (char*)out_all + batch * geo.outStride;
     // a chunk's first output word and its words (a frame or a part of one: the chunk of its own one-chunk decode,
     // whose first stage, 32 frmW0, the run's `start` below carries into the loads and the pad predicate)
@@ -1153,14 +1214,14 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
         // q0 = r0 = 0), or a later part's (no lead stage, frame stage fst - 26)
         const PfrmGroup pg = pfrm_group(fst);
         uint32_t r0;
-        const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base<VB>(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
+        const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base<VB>(pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
         r0 = __builtin_amdgcn_readfirstlane(r0);
         const uint32_t lead = __builtin_amdgcn_readfirstlane(pg.lead);
-        rA = tg_pfr_load<I8>(rs, geo.pun, base4, r0, lead, (uint32_t)sA);
-        rB = tg_pfr_load<I8>(rs, geo.pun, base4, r0, lead, (uint32_t)sB);
+        rA = tg_pfr_load<I8>(rs, pun, base4, r0, lead, (uint32_t)sA);
+        rB = tg_pfr_load<I8>(rs, pun, base4, r0, lead, (uint32_t)sB);
     } else if constexpr (PTB) {  // one resource for the whole frame: its received bytes; the frame's group 0 wraps its lead
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)pfrB, 0x00020000);
-        tg_ptb_load<I8>(rs, geo.pun, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+        tg_ptb_load<I8>(rs, pun, fst, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
     } else if constexpr (PUN) {
         uint32_t r0;
         rs = tg_rsrc_pun(in, start + 32ull * j0, availB, geo.pun, &r0);
@@ -1371,14 +1432,14 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(8))
             __builtin_assume(g0n >= kFrmGroup);  // (no lead stage: pg.lead folds to 0)
             const PfrmGroup pg = pfrm_group(g0n);
             uint32_t r0;
-            const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base<VB>(geo.pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
+            const uint32_t base4 = __builtin_amdgcn_readfirstlane(pfrm_base<VB>(pun, __builtin_amdgcn_readfirstlane(pg.t0), &r0));
             r0 = __builtin_amdgcn_readfirstlane(r0);
-            rA = tg_pfr_load<I8>(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sA);
-            rB = tg_pfr_load<I8>(rs, geo.pun, base4, r0, pg.lead, (uint32_t)sB);
+            rA = tg_pfr_load<I8>(rs, pun, base4, r0, pg.lead, (uint32_t)sA);
+            rB = tg_pfr_load<I8>(rs, pun, base4, r0, pg.lead, (uint32_t)sB);
         } else if constexpr (PTB) {  // the next group's kept values of the extended stream: the frame, wrapped
             const uint32_t g0n = fst + 32u * (j + 3);
             __builtin_assume(g0n >= kFrmGroup);  // (no lead: tb_wrap_group and tb_group_r0 fold to their g0 >= 26 forms)
-            tg_ptb_load<I8>(rs, geo.pun, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
+            tg_ptb_load<I8>(rs, pun, g0n, (uint32_t)sA, (uint32_t)sB, frmS, tbr, rA, rB);
         } else if constexpr (PUN) {  // the next group's received values, at the offsets of its own r0
             uint32_t r0;
             rs = tg_rsrc_pun(in, start + 32ull * (j + 3), availB, geo.pun, &r0);

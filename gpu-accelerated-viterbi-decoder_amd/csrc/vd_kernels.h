@@ -79,6 +79,14 @@ struct Geom {
     // wave; frmPartG = the workgroups per frame (wave wv of workgroup b: part (b % G) kWaves + wv of frame b / G)
     uint32_t frmPartW = 0;
     uint32_t frmPartG = 1;
+    // mixed frames (channel ids kMix + a punctured frame id, vd_kernel_tg.h; vd_frames.h "mixed frames"): frame f decodes
+    // under record mixRate[f] (null: record 0) of the mixN records at mixPat (kMixRecordDwords dwords each; the kernel
+    // reads the table when it runs, so a replayed graph sees the table as it stands then) and starts at value index
+    // mixOff[f] of the received buffer (null: at f * inStride bytes).  Unused, and null, in every other launch.
+    const uint32_t* mixPat = nullptr;
+    const uint8_t* mixRate = nullptr;
+    const uint64_t* mixOff = nullptr;
+    uint32_t mixN = 0;
 };
 // Progress board of the fairness controller: per SIMD slot (XCC, SE, SH, CU, SIMD from the hardware
 // wave id) kFairWaves 32-bit words, one per hardware wave slot of that SIMD (HW_ID.WAVE_ID): the blocks

@@ -251,6 +251,43 @@ VD_BYTE_TABLE(launcher_byte_tb_frames, VD_BYTE_PAIRS)
 #define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + kTb + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + kTb + kPun + C, M, 16>;
 VD_BYTE_TABLE(launcher_byte_punct_tb_frames, VD_BYTE_PUN_PAIRS)
 #undef VD_X
+// Mixed frames (channel ids kMix + a punctured frame id, vd_kernel_tg.h; vd_frames.h "mixed frames"): the mixed-rate
+// twins of the two punctured float tables (9 pairs x {O32, O16} each) and of the two punctured byte tables (5 pairs x
+// {O32, O16} each): 56 kernels, in four tables of their own, planned by plan_frames like every frame launch.
+#define VD_MIX_TABLE(NAME, PAIRS)                                                            \
+    template <class L>                                                                       \
+    typename L::fn NAME(int ch, int me, bool o16)                                            \
+    {                                                                                        \
+        struct Table {                                                                       \
+            typename L::fn at[5][3][2] = {};                                                 \
+            Table()                                                                          \
+            {                                                                                \
+                PAIRS(VD_X)                                                                  \
+            }                                                                                \
+        };                                                                                   \
+        static const Table t;                                                                \
+        return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;         \
+    }
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kFrm + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kFrm + kPun + C, M, 16>;
+VD_MIX_TABLE(launcher_mixed_frames, VD_PUN_PAIRS)
+#undef VD_X
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kFrm + kTb + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kFrm + kTb + kPun + C, M, 16>;
+VD_MIX_TABLE(launcher_mixed_tb_frames, VD_PUN_PAIRS)
+#undef VD_X
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kI8 + kFrm + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kI8 + kFrm + kPun + C, M, 16>;
+VD_MIX_TABLE(launcher_byte_mixed_frames, VD_BYTE_PUN_PAIRS)
+#undef VD_X
+#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kI8 + kFrm + kTb + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kI8 + kFrm + kTb + kPun + C, M, 16>;
+VD_MIX_TABLE(launcher_byte_mixed_tb_frames, VD_BYTE_PUN_PAIRS)
+#undef VD_X
+#undef VD_MIX_TABLE
+// the mixed-rate kernel of the family (tail-biting or padded) for float (i8 false) or int8 values
+template <class L>
+typename L::fn launcher_mixed(bool i8, bool tb, int ch, int me, bool o16)
+{
+    return i8 ? (tb ? launcher_byte_mixed_tb_frames<L>(ch, me, o16) : launcher_byte_mixed_frames<L>(ch, me, o16))
+              : (tb ? launcher_mixed_tb_frames<L>(ch, me, o16) : launcher_mixed_frames<L>(ch, me, o16));
+}
 #undef VD_BYTE_TABLE
 // the byte twin of the family (pun, tb)
 template <class L>
@@ -366,13 +403,16 @@ inline constexpr const char* kCoreNames[3] = {"B32", "B16", "F16"};
 // vd_decoder_kernel_name: the kernel and launch form of one planned launch; input: 0 packed words, 1 float
 // channel values (LLR), 2 punctured float values (PUN), 3 frames of float values (FRM; a plan of plan_frames),
 // 4 punctured frames (FRM+PUN; a plan of plan_frames), 5 tail-biting frames (FRM+TB; a plan of plan_frames),
-// 6 punctured tail-biting frames (FRM+TB+PUN; a plan of plan_frames), 7 .. 10 the int8 twins of 3 .. 6 (FRM+I8+...)
+// 6 punctured tail-biting frames (FRM+TB+PUN; a plan of plan_frames), 7 .. 10 the int8 twins of 3 .. 6 (FRM+I8+...),
+// 11, 12 mixed frames, padded and tail-biting (FRM+MIX+PUN, FRM+MIX+TB+PUN), 13, 14 their int8 twins (FRM+I8+MIX+...)
 inline std::string plan_name(const LaunchPlan& p, int o, int input)
 {
     if (!p.launches) return "-";
-    const bool i8 = input >= 7 && input <= 10;
-    if (i8) input -= 4;  // the float twin's name with I8+ after FRM+
-    const std::string fam = input == 6 ? "TB+PUN+" : input == 5 ? "TB+" : input == 4 ? "PUN+" : "";
+    const bool mix = input >= 11 && input <= 14;
+    const bool i8 = (input >= 7 && input <= 10) || (mix && input >= 13);
+    if (mix) input = (input & 1) ? 4 : 6;  // the punctured family's name with MIX+ before it
+    else if (i8) input -= 4;               // the float twin's name with I8+ after FRM+
+    const std::string fam = std::string(mix ? "MIX+" : "") + (input == 6 ? "TB+PUN+" : input == 5 ? "TB+" : input == 4 ? "PUN+" : "");
     const std::string args = std::string(input >= 3 && input <= 6 ? "FRM+" + std::string(i8 ? "I8+" : "") + fam :
                                          input == 2 ? "PUN+" : input ? "LLR+" : "") +
                              kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," + (out_of(o) ? "O16" : "O32") + ">";

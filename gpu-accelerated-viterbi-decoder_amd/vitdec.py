@@ -50,7 +50,9 @@ EXPORTS = ["vd_options_valid", "vd_input_size", "vd_message_len", "vd_output_siz
            "vd_run_punct", "vd_frame_output_size", "vd_run_device_frames", "vd_run_frames",
            "vd_run_device_punct_frames", "vd_run_punct_frames", "vd_run_device_tb_frames", "vd_run_tb_frames",
            "vd_run_device_punct_tb_frames", "vd_run_punct_tb_frames", "vd_set_frame_part_bits", "vd_frame_part_bits",
-           "vd_run_device_byte_frames", "vd_run_byte_frames"]
+           "vd_run_device_byte_frames", "vd_run_byte_frames", "vd_set_frame_patterns", "vd_frame_patterns",
+           "vd_run_device_mixed_frames", "vd_run_device_byte_mixed_frames", "vd_run_mixed_frames",
+           "vd_run_byte_mixed_frames"]
 
 # puncture patterns (period, keep0, keep1): bit i of keep0 / keep1 = the first (0171) / second (0133) encoder
 # output of the stages t with t % period == i is transmitted.  Any valid masks decode (and equal the rate-1/2
@@ -126,6 +128,11 @@ def lib():
            "vd_run_byte_frames": ([vp, vp, sz, vp, sz, vp, sz, i, i, f, i, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.POINTER(f)], None),
            "vd_set_frame_part_bits": ([vp, sz], None), "vd_frame_part_bits": ([vp, ctypes.POINTER(sz)], None),
+           "vd_set_frame_patterns": ([vp, vp, i], None), "vd_frame_patterns": ([vp, vp, ctypes.POINTER(i)], None),
+           "vd_run_device_mixed_frames": ([vp, vp, sz, vp, vp, sz, vp, vp, sz, i, i, f, vp], None),
+           "vd_run_device_byte_mixed_frames": ([vp, vp, sz, vp, vp, sz, vp, vp, sz, i, i, f, vp], None),
+           "vd_run_mixed_frames": ([vp, vp, sz, vp, sz, vp, sz, vp, vp, sz, i, i, f, ctypes.POINTER(f)], None),
+           "vd_run_byte_mixed_frames": ([vp, vp, sz, vp, sz, vp, sz, vp, vp, sz, i, i, f, ctypes.POINTER(f)], None),
            "vd_kernel_name": ([i], ctypes.c_char_p),
            "vd_decoder_kernel_name": ([vp, sz, i, i], ctypes.c_char_p)}
     for name, (args, res) in sig.items():
@@ -276,7 +283,9 @@ class ViterbiCUDA:
         0 packed input, True / 1 float channel values, 2 punctured float values, 3 a frame launch (inputNum =
         maxFrameBits, nbatch = nframes), 4 a launch of punctured frames (likewise), 5 a launch of tail-biting
         frames (likewise), 6 a launch of punctured tail-biting frames (likewise; "-" on a HARD decoder), 7 .. 10 the
-        int8 twins of 3 .. 6 (run_device_byte_frames; "-" where that call is refused)"""
+        int8 twins of 3 .. 6 (run_device_byte_frames; "-" where that call is refused), 11 / 12 a mixed launch of
+        open or terminated / of tail-biting frames (run_device_mixed_frames), 13 / 14 their int8 twins (likewise "-"
+        where the call is refused)"""
         return lib().vd_decoder_kernel_name(self._h, inputNum, nbatch, int(llr)).decode()
 
     def set_guard_check(self, enable=True):
@@ -573,6 +582,101 @@ class ViterbiCUDA:
                                                output_stride, ctypes.c_void_p(frame_bits_ptr) if frame_bits_ptr else None,
                                                maxFrameBits, nframes, kind, scale, *pattern, ctypes.c_void_p(stream)))
 
+    # ---- frames of mixed code rates in one launch (vd_capi.h "frames of mixed code rates") ----
+    def set_frame_patterns(self, patterns):
+        """The decoder's table of up to 16 puncture patterns (period, keep0, keep1), which the mixed launches index per
+        frame; (1, 1, 1) is a legal entry.  Blocks until the device copy is done; the kernels read the table when they
+        run (a replayed graph sees the table as it stands then).  Not to be called while launches of this decoder
+        are in flight."""
+        t = np.ascontiguousarray(patterns, dtype=np.uint32).reshape(-1)
+        if t.size % 3:
+            raise VitdecError("set_frame_patterns: patterns must be (period, keep0, keep1) triples")
+        _check(lib().vd_set_frame_patterns(self._h, t.ctypes.data if t.size else None, t.size // 3))
+
+    def frame_patterns(self):
+        """the table as a list of (period, keep0, keep1)"""
+        t = np.zeros(48, dtype=np.uint32)
+        n = ctypes.c_int(0)
+        _check(lib().vd_frame_patterns(self._h, t.ctypes.data, ctypes.byref(n)))
+        return [tuple(int(x) for x in t[3 * k:3 * k + 3]) for k in range(n.value)]
+
+    def _run_mixed(self, fn, who, dtype, rx_h, kind, maxFrameBits, scale, frame_bits, rates, offsets):
+        rx_h = np.ascontiguousarray(rx_h, dtype=dtype)
+        if offsets is None:
+            if rx_h.ndim != 2:
+                raise VitdecError(f"{who}: rx_h must be [nframes, L] without offsets")
+            nframes, stride, total, off = rx_h.shape[0], rx_h.shape[1] * rx_h.itemsize, 0, None
+            need = max([punctured_len(p, 2 * maxFrameBits) for p in self.frame_patterns()] or [0])
+            if rx_h.shape[1] < need:
+                raise VitdecError(f"{who}: rows of {rx_h.shape[1]} values, the table's densest pattern needs {need} for "
+                                  f"{maxFrameBits} stages")
+        else:
+            off = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if off.ndim != 1 or rx_h.ndim != 1:
+                raise VitdecError(f"{who}: with offsets rx_h is one flat buffer and offsets holds one index per frame")
+            nframes, stride, total = off.size, 0, rx_h.size
+        row = frame_output_size(self.options, maxFrameBits)
+        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
+        fb = rt = None
+        if frame_bits is not None:
+            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
+            if fb.shape != (nframes,):
+                raise VitdecError(f"{who}: frame_bits must hold one length per frame")
+        if rates is not None:
+            rt = np.ascontiguousarray(rates, dtype=np.uint8)
+            if rt.shape != (nframes,):
+                raise VitdecError(f"{who}: rates must hold one pattern index per frame")
+        if rx_h.size == 0:
+            rx_h = np.zeros(4, dtype=dtype)  # (a buffer to point at: no frame reads a value)
+        ms = ctypes.c_float(0.0)
+        _check(fn(self._h, rx_h.ctypes.data, stride, off.ctypes.data if off is not None else None, total, out.ctypes.data, row,
+                  fb.ctypes.data if fb is not None else None, rt.ctypes.data if rt is not None else None, maxFrameBits,
+                  nframes, kind, scale, ctypes.byref(ms)))
+        return out, ms.value
+
+    def run_mixed_frames(self, rx_h, kind, maxFrameBits, scale=40000.0, frame_bits=None, rates=None, offsets=None):
+        """Blocking decode of nframes frames at mixed code rates in one launch.  Frame f decodes under pattern rates[f]
+        of set_frame_patterns' table (default: pattern 0) with min(frame_bits[f], maxFrameBits) stages; kind:
+        FRAMES_OPEN, FRAMES_TERMINATED or FRAMES_TAILBITING for all of them.  Without offsets rx_h is a float array
+        [nframes, L] with frame f's received values at the start of row f; with offsets it is one flat float buffer and
+        frame f's values start at index offsets[f] (mixed_layout gives back-to-back offsets).  Frame f equals, word
+        for word, run_punct_frames / run_punct_tb_frames of that frame alone under its pattern; a frame of 0 stages or
+        with a rate index outside the table decodes nothing.  SOFT4, SOFT8, SOFT16 and FP32 decoders.  Returns (out,
+        ms) shaped as run_frames does."""
+        return self._run_mixed(lib().vd_run_mixed_frames, "run_mixed_frames", np.float32, rx_h, kind, maxFrameBits, scale,
+                               frame_bits, rates, offsets)
+
+    def run_byte_mixed_frames(self, q_h, kind, maxFrameBits, scale=1.0, frame_bits=None, rates=None, offsets=None):
+        """run_mixed_frames on int8 channel values (row pitch and offsets in bytes): frame f equals run_byte_frames of
+        that frame alone under its pattern -- the punctured path, also for (1, 1, 1), whose words equal the unpunctured
+        one's.  SOFT4 and SOFT8 decoders."""
+        return self._run_mixed(lib().vd_run_byte_mixed_frames, "run_byte_mixed_frames", np.int8, q_h, kind, maxFrameBits,
+                               scale, frame_bits, rates, offsets)
+
+    def run_device_mixed_frames(self, rx_ptr, rx_stride, output_ptr, output_stride, maxFrameBits, nframes, kind,
+                                scale=40000.0, frame_bits_ptr=0, rate_ptr=0, offsets_ptr=0, stream=0):
+        """Async decode of nframes frames at mixed code rates in one launch (vd_run_device_mixed_frames): frame f reads
+        its punctured_len(pattern rate[f], 2 S_f) floats at rx_ptr + f * rx_stride bytes, or with offsets_ptr (a
+        device array of uint64 value indices) from float offsets[f] of rx_ptr on, and writes 4 * ceil(S_f / 32) bytes
+        at output_ptr + f * output_stride.  rate_ptr: a device array of uint8 pattern indices (0: pattern 0 for all);
+        frame_bits_ptr as in run_device_frames."""
+        vp = ctypes.c_void_p
+        _check(lib().vd_run_device_mixed_frames(self._h, vp(rx_ptr), rx_stride, vp(offsets_ptr) if offsets_ptr else None,
+                                                vp(output_ptr), output_stride, vp(frame_bits_ptr) if frame_bits_ptr else None,
+                                                vp(rate_ptr) if rate_ptr else None, maxFrameBits, nframes, kind, scale,
+                                                vp(stream)))
+
+    def run_device_byte_mixed_frames(self, q_ptr, q_stride, output_ptr, output_stride, maxFrameBits, nframes, kind,
+                                     scale=1.0, frame_bits_ptr=0, rate_ptr=0, offsets_ptr=0, stream=0):
+        """run_device_mixed_frames on int8 channel values (vd_run_device_byte_mixed_frames): strides and offsets in
+        bytes, any address."""
+        vp = ctypes.c_void_p
+        _check(lib().vd_run_device_byte_mixed_frames(self._h, vp(q_ptr), q_stride, vp(offsets_ptr) if offsets_ptr else None,
+                                                     vp(output_ptr), output_stride,
+                                                     vp(frame_bits_ptr) if frame_bits_ptr else None,
+                                                     vp(rate_ptr) if rate_ptr else None, maxFrameBits, nframes, kind, scale,
+                                                     vp(stream)))
+
 
 class PinnedArray:
     """A numpy view of page-locked host memory from vd_host_alloc (freed with the object)."""
@@ -623,6 +727,21 @@ def depuncture(rx, pattern, inputNum):
     out = np.zeros(inputNum, dtype=np.float32)
     out[:kept.size][kept] = np.asarray(rx, dtype=np.float32).reshape(-1)[:int(kept.sum())]
     return out
+
+
+def mixed_layout(lengths, rates, patterns):
+    """(offsets, total) of frames laid back to back in one received buffer: frame f of lengths[f] stages under
+    patterns[rates[f]] holds punctured_len(that pattern, 2 * lengths[f]) values from index offsets[f] on; a frame whose
+    rate index lies outside patterns holds none.  offsets: uint64 array, total: the values of the buffer."""
+    offs, at = np.zeros(len(lengths), dtype=np.uint64), 0
+    for f, (S, r) in enumerate(zip(lengths, rates)):
+        offs[f] = at
+        if 0 <= int(r) < len(patterns):
+            period, keep0, keep1 = patterns[int(r)]
+            kp = bin(keep0).count("1") + bin(keep1).count("1")
+            low = (1 << (int(S) % period)) - 1
+            at += int(S) // period * kp + bin(keep0 & low).count("1") + bin(keep1 & low).count("1")
+    return offs, at
 
 
 def frame_output_size(options, frameBits):

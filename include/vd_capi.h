@@ -181,9 +181,10 @@ int vd_run_punct(vd_decoder* dec, const float* rx_h, void* output_h, size_t inpu
  * [1, 2^20], nframes < 1, scale not finite and > 0, a misaligned pointer or stride, overlapping frames.
  * Punctured frames: vd_run_device_punct_frames below; tail-biting frames: vd_run_device_tb_frames below; punctured
  * tail-biting frames: vd_run_device_punct_tb_frames below.
- * Frames of int8 channel values are supported: vd_run_device_byte_frames below, for all four families.  The
- * reference's MSB-first packed words as frame input, int16 frames, frames longer than 2^20 stages and vd_decode_pk
- * twins of the frame kernels are not. */
+ * Frames of int8 channel values are supported: vd_run_device_byte_frames below, for all four families; frames of
+ * mixed code rates and per-frame offsets in one launch: vd_run_device_mixed_frames below.  The reference's MSB-first
+ * packed words as frame input, int16 frames, frames longer than 2^20 stages and vd_decode_pk twins of the frame
+ * kernels are not. */
 
 /* bytes a frame of frameBits stages decodes to: 4 * ceil(frameBits / 32), for O_B32 and O_B16 alike */
 size_t vd_frame_output_size(int options, size_t frameBits);
@@ -368,6 +369,63 @@ int vd_run_byte_frames(vd_decoder* dec, const int8_t* q_h, size_t q_stride, void
                        const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int kind, float scale, int period,
                        uint32_t keep0, uint32_t keep1, float* kernel_ms);
 
+/* ---- frames of mixed code rates in one launch (new: one 802.11 slot or 802.16 burst set holds packets at rates 1/2,
+ *      2/3, 3/4 and 5/6, of different lengths, their soft values back to back) ----
+ * A decoder holds a table of up to 16 puncture patterns.  A mixed launch decodes nframes frames of one kind
+ * (VD_FRAMES_OPEN, VD_FRAMES_TERMINATED or VD_FRAMES_TAILBITING, for the whole launch), frame f under pattern
+ * rate_d[f] of the table (pattern 0 when rate_d is NULL), with S_f = min(frame_bits_d[f], maxFrameBits) stages
+ * (maxFrameBits when frame_bits_d is NULL).  Frame f reads exactly vd_punctured_len(pattern_f, 2 S_f) values: at rx_d +
+ * f * rx_stride bytes when rx_offsets_d is NULL, else from value index rx_offsets_d[f] of rx_d on -- an index in
+ * values (floats, or bytes for int8), not a byte offset, so every offset is aligned by construction; rx_stride is
+ * then ignored, the offsets may come in any order, and two frames may share input.  It writes exactly
+ * vd_frame_output_size(S_f) bytes at output_d + f * output_stride.  A frame with S_f = 0 or rate_d[f] >= the
+ * table's length reads nothing and writes nothing.  Frame f's words equal, word for word, those of
+ * vd_run_device_punct_frames (open, terminated) or vd_run_device_punct_tb_frames (tail-biting) of that frame alone
+ * under its pattern, and for int8 those of vd_run_device_byte_frames under a pattern other than (1, 1, 1).  (1, 1, 1)
+ * is a legal entry -- rate-1/2 frames belong in a mixed batch -- and goes through the same punctured path with
+ * single-value loads: its words equal the unpunctured family's, rx_d needs 4-byte alignment only, and the int8 twin
+ * has no 2-byte alignment rule.  The decoder's part length (vd_set_frame_part_bits) applies as everywhere: the grid
+ * comes from maxFrameBits, and all parts of a frame share its pattern and offset.
+ * The kernels (vd_decode_tg<FRM+MIX+...>) read the table on the device when they run.  A captured graph therefore
+ * decodes under the table as it stands at replay, not as it stood at capture -- unlike the part length, which is
+ * read on the host when the entry point is called.
+ * VD_ERR_OPTIONS: a HARD decoder (a punctured value has no hard code); a SOFT16 or FP32 decoder for the int8 twin.
+ * VD_ERR_ARG: an empty table, a kind outside 0 .. 2, maxFrameBits outside [1, 2^20], nframes < 1, a scale the
+ * family rejects (finite and > 0; open and terminated frames also need -65536 / scale finite), rx_d not 4-byte
+ * aligned or (without offsets) rx_stride % 4 for floats, output_stride % 4, with nframes > 1 an output_stride <
+ * vd_frame_output_size(maxFrameBits) or (without offsets) an rx_stride below the received bytes of a maxFrameBits
+ * frame under the table's densest pattern, and the workgroup limit of frames in parts. */
+
+/* Stores n patterns, 0 <= n <= 16, given as n (period, keep0, keep1) triples, as the decoder's table (host copy and
+ * device records; the device buffer is the feature's only allocation, made by the first call and freed by vd_destroy).
+ * VD_ERR_ARG: n outside [0, 16], triples NULL with n > 0, a pattern vd_punctured_len would reject; the table is then
+ * unchanged.  Blocks until the copy is done.  Do not call it while launches of this decoder are in flight. */
+int vd_set_frame_patterns(vd_decoder* dec, const uint32_t* triples, int n);
+/* reads the table back: *n patterns, their triples into triples (room for 48 values; NULL: the count only) */
+int vd_frame_patterns(vd_decoder* dec, uint32_t* triples, int* n);
+/* nframes frames of float values at mixed rates in one launch, under the rules of vd_run_device_frames (asynchronous,
+ * no allocation, capturable, the stream on the decoder's device) */
+int vd_run_device_mixed_frames(vd_decoder* dec, const float* rx_d, size_t rx_stride,
+                               const uint64_t* rx_offsets_d /* device, or NULL: frame f at f * rx_stride bytes */,
+                               void* output_d, size_t output_stride,
+                               const uint32_t* frame_bits_d /* device, or NULL: every frame has maxFrameBits */,
+                               const uint8_t* rate_d /* device, or NULL: every frame uses pattern 0 */,
+                               size_t maxFrameBits, int nframes, int kind, float scale, void* stream);
+/* its int8 twin (SOFT4 and SOFT8 decoders): strides in bytes, offsets in bytes, any address */
+int vd_run_device_byte_mixed_frames(vd_decoder* dec, const int8_t* q_d, size_t q_stride, const uint64_t* q_offsets_d,
+                                    void* output_d, size_t output_stride, const uint32_t* frame_bits_d, const uint8_t* rate_d,
+                                    size_t maxFrameBits, int nframes, int kind, float scale, void* stream);
+/* Blocking host-to-host variants over host arrays of the same layout (H2D, the launch, D2H); the output bytes no frame
+ * writes keep their values.  Without offsets the buffer ends with a maxFrameBits frame under the table's densest
+ * pattern, as the stride rule has it; with offsets it holds rx_total values (ignored otherwise), and a frame that does
+ * not lie inside them is VD_ERR_ARG.  kernel_ms as in vd_run. */
+int vd_run_mixed_frames(vd_decoder* dec, const float* rx_h, size_t rx_stride, const uint64_t* rx_offsets_h, size_t rx_total,
+                        void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h,
+                        size_t maxFrameBits, int nframes, int kind, float scale, float* kernel_ms);
+int vd_run_byte_mixed_frames(vd_decoder* dec, const int8_t* q_h, size_t q_stride, const uint64_t* q_offsets_h, size_t q_total,
+                             void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h,
+                             size_t maxFrameBits, int nframes, int kind, float scale, float* kernel_ms);
+
 /* ---- the reference harness's channel source (RandBitGen | ConvolutionalEncoder | AddNoise |
  *      SoftDecisionPacker, viterbiDF.h:20-167), host and GPU ---- */
 
@@ -425,7 +483,11 @@ const char* vd_kernel_name(int options);
  * vd_run_device_punct_tb_frames (vd_decode_tg<FRM+TB+PUN+...>), inputNum and nbatch as for llr 3, "-" on a HARD
  * decoder; llr 7 .. 10: the launch of vd_run_device_byte_frames that is the int8 twin of llr 3 .. 6 (the twin's name
  * with I8+ after FRM+, e.g. vd_decode_tg<FRM+I8+TB+PUN+...>), "-" where that call returns VD_ERR_OPTIONS (SOFT16 and
- * FP32 decoders; llr 8 and 10 on a HARD decoder); valid until the thread's next call */
+ * FP32 decoders; llr 8 and 10 on a HARD decoder); llr 11, 12: the launch of vd_run_device_mixed_frames for open or
+ * terminated frames (vd_decode_tg<FRM+MIX+PUN+...>) and for tail-biting frames (vd_decode_tg<FRM+MIX+TB+PUN+...>), llr
+ * 13, 14: those of vd_run_device_byte_mixed_frames (vd_decode_tg<FRM+I8+MIX+...>), inputNum and nbatch as for llr 3,
+ * "-" where the call returns VD_ERR_OPTIONS (HARD decoders; llr 13 and 14 on SOFT16 and FP32 decoders); valid until
+ * the thread's next call */
 const char* vd_decoder_kernel_name(vd_decoder* dec, size_t inputNum, int nbatch, int llr);
 /* build record: "<16 hex digits of the SHA-256 of the concatenated sources> <their paths, relative to the
  * package directory>"; the Python binding refuses a library whose sources have changed since (stale build) */

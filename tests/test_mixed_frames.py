@@ -1,0 +1,93 @@
+"""Mixed frames on the CPU: the pattern table's records, the largest received length over a table, mixed_table_error and
+mixed_args_error message by message, the 56 kernels of the mixed launches' tables and their names (csrc/vd_frames.h
+"mixed frames", vd_plan.h; checked by tests/cxx/mixed_frames_check.cpp against a plain enumeration, built stand-alone with
+the host sanitizers), vitdec.mixed_layout against the binding's own puncturer, and the header, the exports and the
+binding's declarations.  The decodes on the GPU: tests/test_gpu_mixed_frames.py."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+# the table of the GPU tests: rates 1/2, 2/3, 3/4, 7/8 on period 7, a period-16 pattern, and one that keeps 1 value in 32
+TABLE = [(1, 1, 1), (2, 1, 3), (3, 5, 3), (7, 0x51, 0x2F), (16, 0xA5C3, 0x5A3D), (16, 0x8000, 0)]
+SIZES = [1, 2, 15, 31, 32, 33, 69, 70, 71, 95, 96, 97, 250, 1000]
+NEW = ["vd_set_frame_patterns", "vd_frame_patterns", "vd_run_device_mixed_frames", "vd_run_device_byte_mixed_frames",
+       "vd_run_mixed_frames", "vd_run_byte_mixed_frames"]
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_records_lengths_arguments_tables_and_names_against_enumeration(tmp_path):
+    exe = tmp_path / "mixed_frames_check"
+    src = os.path.join(ROOT, "tests", "cxx", "mixed_frames_check.cpp")
+    csrc = os.path.join(ROOT, "gpu-accelerated-viterbi-decoder_amd", "csrc")
+    r = subprocess.run([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-Xarch_host",
+                        "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-I", csrc, src,
+                        "-o", str(exe)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    args = ["sizes=" + ",".join(str(s) for s in SIZES)] + [f"pat={p[0]},{p[1]},{p[2]}" for p in TABLE]
+    r = subprocess.run([str(exe)] + args, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip() == f"ok {len(SIZES)} sizes {len(TABLE)} patterns", (r.stdout[-2000:], r.stderr[-2000:])
+
+
+def test_mixed_layout_places_the_frames_back_to_back(vd):
+    """offsets and total equal what laying the punctured frames one after another gives, frame by frame: the length of
+    vitdec.puncture's output for every pattern and length, 0 for a frame whose rate index lies outside the table"""
+    rng = np.random.default_rng(5)
+    lengths = [int(s) for s in SIZES] + [0, 1000, 7] + [int(x) for x in rng.integers(0, 400, 20)]
+    rates = [f % len(TABLE) for f in range(len(lengths))]
+    rates[3], rates[9] = len(TABLE), 255
+    offs, total = vd.mixed_layout(lengths, rates, TABLE)
+    assert offs.dtype == np.uint64 and offs.shape == (len(lengths),)
+    at = 0
+    for f, (S, r) in enumerate(zip(lengths, rates)):
+        assert int(offs[f]) == at, f
+        if r < len(TABLE):
+            n = vd.puncture(np.zeros(2 * S, dtype=np.float32), TABLE[r]).size
+            assert n == vd.punctured_len(TABLE[r], 2 * S)
+            at += n
+    assert total == at
+    # every pattern meets every length
+    for p in range(len(TABLE)):
+        o, t = vd.mixed_layout(SIZES, [p] * len(SIZES), TABLE)
+        want = [vd.punctured_len(TABLE[p], 2 * S) for S in SIZES]
+        assert t == sum(want) and [int(x) for x in o] == [sum(want[:k]) for k in range(len(SIZES))]
+    o, t = vd.mixed_layout([], [], TABLE)
+    assert o.size == 0 and t == 0
+
+
+def test_header_exports_and_binding_agree(vd):
+    src = open(os.path.join(ROOT, "include", "vd_capi.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = set(re.findall(r"\b(vd_[a-z_0-9]+)\s*\(", code))
+    assert set(NEW) <= declared and set(NEW) <= set(vd.EXPORTS)
+    L = vd.lib()
+    want = {"vd_set_frame_patterns": 3, "vd_frame_patterns": 3, "vd_run_device_mixed_frames": 13,
+            "vd_run_device_byte_mixed_frames": 13, "vd_run_mixed_frames": 14, "vd_run_byte_mixed_frames": 14}
+    for n, k in want.items():
+        assert len(getattr(L, n).argtypes) == k, n
+        # ... as many as the header's declaration has parameters
+        decl = re.search(rf"\b{n}\s*\((.*?)\)\s*;", code, flags=re.S).group(1)
+        assert decl.count(",") + 1 == k, (n, decl)
+    for meth in ("set_frame_patterns", "frame_patterns", "run_mixed_frames", "run_device_mixed_frames",
+                 "run_byte_mixed_frames", "run_device_byte_mixed_frames"):
+        assert callable(getattr(vd.ViterbiCUDA, meth))
+    assert callable(vd.mixed_layout)
+    # the sentence that lists what frames do not support names the mixed launch as supported
+    assert "vd_run_device_mixed_frames below" in src and "llr 11, 12" in src
+
+
+def test_the_gpu_cases_meet_every_pattern_with_every_length():
+    """a self-check of how tests/test_gpu_mixed_frames.py builds its parity cases (it runs no product code): the 99
+    consecutive positions of one option's walk cover all 84 (pattern, length) pairs, and neighbouring frames differ in
+    both"""
+    from test_gpu_mixed_frames import LAUNCHES, pairs_from
+    from test_gpu_mixed_frames import SIZES as GPU_SIZES, TABLE as GPU_TABLE
+    assert GPU_TABLE == TABLE and GPU_SIZES == SIZES
+    for c0 in (0, 7, 33 * 2 + 7 * 17):
+        assert len(set(pairs_from(c0, 3 * sum(LAUNCHES)))) == len(TABLE) * len(SIZES)
+    ps = pairs_from(0, 24)
+    assert all(a[0] != b[0] and a[1] != b[1] for a, b in zip(ps, ps[1:]))
