@@ -2,7 +2,8 @@
 Gaussian noise, and the contract of a frame decode -- the oracle's one-chunk decode (nchunks = 1, O_B16 policy
 0) of the SoftDecisionPacker packing of vitdec.pad_frame(frame values) -- with the oracle's words computed once
 per (option, frame set) and read-only.  Random draws come from np.random.default_rng(seed), one generator per
-call."""
+call.  At SCALE these inputs saturate SOFT4, SOFT8 and FP32 at every value (no rounding or limit decides a word):
+the values that do are in value_patterns.py."""
 import functools
 
 import numpy as np
