@@ -266,13 +266,11 @@ const char* vd_decoder_kernel_name(vd_decoder* d, size_t inputNum, int nbatch, i
     static thread_local std::string name;
     if (!d || nbatch < 1) return "-";
     if (llr == 2 && ch_of(d->options) == HARD) return "-";  // no punctured HARD kernels
-    if (llr == 4 && ch_of(d->options) == HARD) return "-";  // ... nor punctured HARD frames
-    if (llr == 6 && ch_of(d->options) == HARD) return "-";  // ... nor punctured tail-biting HARD frames
-    // the int8 twins of 3 .. 6 (7 .. 10): HARD, SOFT4 and SOFT8 decoders, the punctured ones not on HARD
-    if (llr >= 7 && llr <= 10 && (ch_of(d->options) > SOFT8 || (ch_of(d->options) == HARD && (llr == 8 || llr == 10)))) return "-";
-    // mixed frames (11, 12; their int8 twins 13, 14): punctured kernels, so not on HARD; int8 on SOFT4 and SOFT8 only
-    if (llr >= 11 && llr <= 14 && (ch_of(d->options) == HARD || (llr >= 13 && ch_of(d->options) > SOFT8))) return "-";
-    if (llr >= 3 && llr <= 14) {  // a frame launch (4: of punctured, 5: of tail-biting, 6: of punctured tail-biting frames): inputNum = maxFrameBits, nbatch = nframes
+    if (llr >= 3 && llr <= 14) {  // a frame launch of the code's family (frame_family_of_input): inputNum = maxFrameBits, nbatch = nframes
+        // "-" where the family has no kernel for the decoder's format (launcher_frames: no punctured HARD frames, int8
+        // on HARD, SOFT4 and SOFT8 only), which is where the entry point refuses by format
+        const int o = d->options;
+        if (!launcher_frames<Launch>(frame_family_of_input(llr), ch_of(o), met_of(o), out_of(o) == 1)) return "-";
         if (inputNum < 1 || inputNum > kFrmMaxBits) return "-";
         if (frame_parts_error(inputNum, nbatch, d->partBits)) return "-";  // (more workgroups than a launch can have)
         name = plan_name(plan_frames(d->options, (uint64_t)nbatch, frame_parts((uint32_t)inputNum, frame_part_words(d->partBits))),
@@ -584,47 +582,74 @@ int vd_frame_part_bits(vd_decoder* d, size_t* partBits)
     return VD_OK;
 }
 
-// the argument checks of a frame decode: VD_ERR_ARG / VD_ERR_OPTIONS
-static int frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, const void* output, size_t output_stride,
-                       size_t maxFrameBits, int nframes, int terminated, float scale, bool device)
+static_assert(kFrameErrOptions == VD_ERR_OPTIONS && kFrameErrArg == VD_ERR_ARG && kByteFramesOpen == VD_FRAMES_OPEN &&
+                  kByteFramesTerminated == VD_FRAMES_TERMINATED && kByteFramesTailbiting == VD_FRAMES_TAILBITING,
+              "vd_frames.h mirrors these");
+
+// One call of a frame entry point: what the check goes by (vd_frames.h FrameArgs, the family first) and the buffers --
+// the device ones of a launch, or the host ones of a blocking variant, laid out alike.
+struct FrameCall {
+    FrameArgs a;
+    const void* in;            // the values: floats, or int8 (a.fam.i8)
+    void* out;
+    const uint32_t* bits;      // the frames' lengths, or null: every frame has maxFrameBits stages
+    const uint8_t* rate;       // mixed launches: the frames' pattern indices, or null: pattern 0
+    const uint64_t* off;       // ... and their offsets in values, or null: frames at f strides
+};
+// the record of the family's entry point: plain frames and tail-biting frames carry pattern (1, 1, 1), a mixed
+// launch sets its two arrays itself
+static FrameCall frame_call(FrameFamily fam, const void* in, size_t stride, void* out, size_t outStride, const uint32_t* bits,
+                            size_t maxFrameBits, int nframes, int kind, float scale, int period = 1, uint32_t keep0 = 1,
+                            uint32_t keep1 = 1)
 {
-    if (!d || !llr || !output) return fail(VD_ERR_ARG, "null argument");
-    if (const char* why = frame_args_error(device ? (uint64_t)(uintptr_t)llr : 0, llr_stride, output_stride, maxFrameBits,
-                                           nframes, scale))
-        return fail(VD_ERR_ARG, why);
-    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
-    if (ch_of(d->options) == HARD && !terminated)
-        return fail(VD_ERR_OPTIONS, "open frames on a HARD decoder: the stages after an open frame are erasures, and HARD's "
-                                    "v > 0 ? 1 : 0 has no neutral code; terminate the frames or use SOFT4, SOFT8, SOFT16 or FP32");
+    FrameCall c = {};
+    c.a.fam = fam;
+    c.a.stride = stride;
+    c.a.outStride = outStride;
+    c.a.maxFrameBits = maxFrameBits;
+    c.a.nframes = nframes;
+    c.a.kind = kind;
+    c.a.scale = scale;
+    c.a.period = period;
+    c.a.keep0 = keep0;
+    c.a.keep1 = keep1;
+    c.in = in;
+    c.out = out;
+    c.bits = bits;
+    return c;
+}
+static FrameFamily byte_family(int kind, int period, uint32_t keep0, uint32_t keep1)
+{
+    return {!byte_frames_unpunctured(period, keep0, keep1), kind == kByteFramesTailbiting, true, false};
+}
+
+// The checks of every frame entry point (VD_ERR_ARG / VD_ERR_OPTIONS): a null pointer, then frame_args_error on the
+// call and the decoder's format, part length and pattern table.  The part length is read here, on the host, once per
+// call: a captured graph keeps the value it was captured with.  device: c.in is a device address and its alignment
+// counts (the blocking variants stage into the decoder's own buffers).
+static int check_frames(const vd_decoder* d, FrameCall& c, bool device)
+{
+    if (!d || !c.in || !c.out) return fail(VD_ERR_ARG, "null argument");
+    c.a.addr = device ? (uint64_t)(uintptr_t)c.in : 0;
+    c.a.offsets = c.off != nullptr;
+    c.a.options = d->options;
+    c.a.partBits = d->partBits;
+    c.a.table = d->mixTab;
+    c.a.tableN = d->mixN;
+    int code = VD_OK;
+    if (const char* why = frame_args_error(c.a, &code)) return fail(code, why);
     return VD_OK;
 }
 
-// a mixed launch's per-frame arrays (device; null: pattern 0 / frames at f strides)
-struct MixArgs {
-    const uint8_t* rate_d;
-    const uint64_t* off_d;
-};
-
-// the one launch of checked arguments; pun: the frames hold the kept values of punctured frames, tb: the frames
-// are tail-biting (no pad: terminated means nothing), both: punctured tail-biting frames (vd_frames.h)
-// i8: the frames hold int8 values, llr_stride counts their bytes (vd_frames.h "int8 frames")
-// mix: frames of mixed code rates under the decoder's pattern table (vd_frames.h "mixed frames"; pun is then null)
-static int launch_frames_checked(vd_decoder* d, const void* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
-                                 const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
-                                 hipStream_t s, const Punct* pun = nullptr, bool tb = false, bool i8 = false,
-                                 const MixArgs* mix = nullptr)
+// the one launch of a checked call on device buffers
+static int launch_frames_checked(vd_decoder* d, const FrameCall& c, hipStream_t s)
 {
     const int options = d->options;
-    // the decoder's part length, read here, on the host: a captured graph keeps the value it was captured with
-    const uint32_t partBits = d->partBits;
-    if (const char* why = frame_parts_error(maxFrameBits, nframes, partBits)) return fail(VD_ERR_ARG, why);
-    const LaunchPlan p = plan_frames(options, (uint64_t)nframes, frame_parts((uint32_t)maxFrameBits, frame_part_words(partBits)));
-    launch_fn f = mix ? launcher_mixed<Launch>(i8, tb, ch_of(options), met_of(options), out_of(options) == 1)
-                  : i8 ? launcher_byte<Launch>(pun != nullptr, tb, ch_of(options), met_of(options), out_of(options) == 1)
-                  : tb && pun ? launcher_punct_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
-                  : tb  ? launcher_tb_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
-                  : pun ? launcher_punct_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1)
-                        : launcher_frames<Launch>(ch_of(options), met_of(options), out_of(options) == 1);
+    const FrameFamily fam = c.a.fam;
+    const uint32_t partBits = (uint32_t)c.a.partBits;
+    const LaunchPlan p = plan_frames(options, (uint64_t)c.a.nframes,
+                                     frame_parts((uint32_t)c.a.maxFrameBits, frame_part_words(partBits)));
+    launch_fn f = launcher_frames<Launch>(fam, ch_of(options), met_of(options), out_of(options) == 1);
     if (!f || !p.launches) return fail(VD_ERR_OPTIONS, "invalid options");
     int sdev = -1;
     if (s) VD_HIP(hipStreamGetDevice(s, &sdev));
@@ -636,337 +661,160 @@ static int launch_frames_checked(vd_decoder* d, const void* llr_d, size_t llr_st
     g.packNum = 0;
     g.availStages = 0;
     g.nchunks = 1;
-    g.scale = scale;
+    g.scale = c.a.scale;
     g.fair = d->ds->board;
     g.check = d->check;
-    g.nbatch = (uint32_t)nframes;
-    g.inStride = llr_stride;
-    g.outStride = output_stride;
-    g.frmBits = frame_bits_d;
-    g.frmMax = (uint32_t)maxFrameBits;
-    g.frmTerm = terminated ? 1u : 0u;
-    if (!tb) frame_pad(scale, &g.frmPad);  // (checked by the caller)
-    if (pun) g.pun = *pun;
-    if (mix) {  // the table as a device pointer: read by the kernel when it runs
+    g.nbatch = (uint32_t)c.a.nframes;
+    g.inStride = c.a.stride;
+    g.outStride = c.a.outStride;
+    g.frmBits = c.bits;
+    g.frmMax = (uint32_t)c.a.maxFrameBits;
+    g.frmTerm = c.a.kind == kByteFramesTerminated ? 1u : 0u;
+    if (!fam.tb) frame_pad(c.a.scale, &g.frmPad);  // (checked)
+    if (fam.mix) {  // the table as a device pointer: read by the kernel when it runs
         g.mixPat = (const uint32_t*)d->mixTab_d;
         g.mixN = (uint32_t)d->mixN;
-        g.mixRate = mix->rate_d;
-        g.mixOff = mix->off_d;
+        g.mixRate = c.rate;
+        g.mixOff = c.off;
+    } else if (fam.pun) {
+        g.pun = punct_make(c.a.period, c.a.keep0, c.a.keep1);
     }
     if (p.parts > 1) {  // (one part: the grid and the arguments of a whole-frame launch)
         g.frmPartW = frame_part_words(partBits);
         g.frmPartG = frame_part_groups(p.parts);
     }
-    f(llr_d, output_d, g, p.grid, s);
+    f(c.in, c.out, g, p.grid, s);
     VD_HIP(hipGetLastError());
     return VD_OK;
 }
 
-// the checks, then the one launch
-static int launch_frames(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
-                         const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
-                         hipStream_t s)
+// The blocking decode of a checked call on host buffers laid out like the device ones: nframes frames at the call's
+// strides, the last frame's part ending with the values of a maxFrameBits frame (frame_value_bytes) and its output
+// words; with offsets, total values in all.  The staging buffers are the decoder's; the offsets (8 bytes each), the
+// lengths (4) and the rate indices (1) ride behind the values from the next 16-byte boundary.  Kernel-only time.
+static int run_frames_staged(vd_decoder* d, FrameCall c, size_t total, float* kernel_ms)
 {
-    int rc = frames_args(d, llr_d, llr_stride, output_d, output_stride, maxFrameBits, nframes, terminated, scale, true);
+    const size_t n = (size_t)c.a.nframes;
+    const size_t inB = c.off ? total * (c.a.fam.i8 ? 1 : 4)
+                             : (n - 1) * c.a.stride + frame_value_bytes(c.a, (uint32_t)c.a.maxFrameBits);
+    const size_t outB = (n - 1) * c.a.outStride + vd_frame_output_size(d->options, c.a.maxFrameBits);
+    const size_t offOff = (inB + 15) & ~(size_t)15, offB = c.off ? n * 8 : 0;
+    const size_t lenOff = offOff + offB, lenB = c.bits ? n * 4 : 0;
+    const size_t rateOff = lenOff + lenB, rateB = c.rate ? n : 0;
+    VD_HIP(hipSetDevice(d->device));
+    int rc = grow(d->llr_d, d->cap_llr, rateOff + rateB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
+    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
     if (rc != VD_OK) return rc;
-    return launch_frames_checked(d, llr_d, llr_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes, terminated,
-                                 scale, s);
+    char* const in_d = (char*)d->llr_d;
+    void* const out_h = c.out;
+    if (inB) VD_HIP(hipMemcpyAsync(in_d, c.in, inB, hipMemcpyHostToDevice, d->stream));
+    if (c.off) VD_HIP(hipMemcpyAsync(in_d + offOff, c.off, offB, hipMemcpyHostToDevice, d->stream));
+    if (c.bits) VD_HIP(hipMemcpyAsync(in_d + lenOff, c.bits, lenB, hipMemcpyHostToDevice, d->stream));
+    if (c.rate) VD_HIP(hipMemcpyAsync(in_d + rateOff, c.rate, rateB, hipMemcpyHostToDevice, d->stream));
+    // the words no frame writes (between the frames, of short, empty and out-of-table frames) keep the caller's values
+    VD_HIP(hipMemcpyAsync(d->out_d, out_h, outB, hipMemcpyHostToDevice, d->stream));
+    c.in = in_d;
+    c.out = d->out_d;
+    if (c.off) c.off = (const uint64_t*)(in_d + offOff);
+    if (c.bits) c.bits = (const uint32_t*)(in_d + lenOff);
+    if (c.rate) c.rate = (const uint8_t*)(in_d + rateOff);
+    VD_HIP(hipEventRecord(d->ev0, d->stream));
+    rc = launch_frames_checked(d, c, d->stream);
+    if (rc != VD_OK) return rc;
+    VD_HIP(hipEventRecord(d->ev1, d->stream));
+    VD_HIP(hipMemcpyAsync(out_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
+    VD_HIP(hipStreamSynchronize(d->stream));
+    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
+    return VD_OK;
+}
+
+// the two ways an entry point ends: check and launch, check and run
+static int launch_frames(vd_decoder* d, FrameCall c, void* stream)
+{
+    const int rc = check_frames(d, c, true);
+    return rc != VD_OK ? rc : launch_frames_checked(d, c, (hipStream_t)stream);
+}
+static int run_frames(vd_decoder* d, FrameCall c, float* kernel_ms)
+{
+    const int rc = check_frames(d, c, false);
+    return rc != VD_OK ? rc : run_frames_staged(d, c, 0, kernel_ms);
 }
 
 int vd_run_device_frames(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
                          const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
                          void* stream)
 {
-    return launch_frames(d, llr_d, llr_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes, terminated, scale,
-                         (hipStream_t)stream);
+    return launch_frames(d, frame_call({false, false, false, false}, llr_d, llr_stride, output_d, output_stride, frame_bits_d,
+                                       maxFrameBits, nframes, terminated ? 1 : 0, scale), stream);
 }
-
-// the host buffers laid out like the device ones: nframes frames at llr_stride / output_stride bytes (the last
-// frame's part ends with its maxFrameBits stages / words); the staging buffers are the decoder's, the lengths
-// ride behind the floats
 int vd_run_frames(vd_decoder* d, const float* llr_h, size_t llr_stride, void* output_h, size_t output_stride,
                   const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int terminated, float scale,
                   float* kernel_ms)
 {
-    int rc = frames_args(d, llr_h, llr_stride, output_h, output_stride, maxFrameBits, nframes, terminated, scale, false);
-    if (rc != VD_OK) return rc;
-    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
-    const size_t inB = (size_t)(nframes - 1) * llr_stride + 8 * maxFrameBits;
-    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
-    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
-    VD_HIP(hipSetDevice(d->device));
-    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB);
-    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
-    if (rc != VD_OK) return rc;
-    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
-    VD_HIP(hipMemcpyAsync(d->llr_d, llr_h, inB, hipMemcpyHostToDevice, d->stream));
-    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
-    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
-    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    rc = launch_frames(d, (const float*)d->llr_d, llr_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes, terminated,
-                       scale, d->stream);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return VD_OK;
+    return run_frames(d, frame_call({false, false, false, false}, llr_h, llr_stride, output_h, output_stride, frame_bits_h,
+                                    maxFrameBits, nframes, terminated ? 1 : 0, scale), kernel_ms);
 }
 
-// ---- punctured frames (vd_frames.h "punctured frames"; vd_decode_tg<FRM+PUN+...>, one frame per wave) ----
-// the argument checks of a punctured frame decode: VD_ERR_ARG / VD_ERR_OPTIONS, or *pn filled in
-static int punct_frames_args(const vd_decoder* d, const void* rx, size_t rx_stride, const void* output, size_t output_stride,
-                             size_t maxFrameBits, int nframes, float scale, int period, uint32_t keep0, uint32_t keep1,
-                             bool device, Punct* pn)
-{
-    if (!d || !rx || !output) return fail(VD_ERR_ARG, "null argument");
-    if (const char* why = pfrm_args_error(device ? (uint64_t)(uintptr_t)rx : 0, rx_stride, output_stride, maxFrameBits, nframes,
-                                          scale, period, keep0, keep1))
-        return fail(VD_ERR_ARG, why);
-    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
-    if (ch_of(d->options) == HARD)
-        return fail(VD_ERR_OPTIONS, "punctured frames on a HARD decoder: a punctured value must decode as code 0 = value 0, "
-                                    "and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");
-    *pn = punct_make(period, keep0, keep1);
-    return VD_OK;
-}
-
+// ---- punctured frames (vd_frames.h "punctured frames"; vd_decode_tg<FRM+PUN+...>) ----
 int vd_run_device_punct_frames(vd_decoder* d, const float* rx_d, size_t rx_stride, void* output_d, size_t output_stride,
                                const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int terminated, float scale,
                                int period, uint32_t keep0, uint32_t keep1, void* stream)
 {
-    Punct pn;
-    int rc = punct_frames_args(d, rx_d, rx_stride, output_d, output_stride, maxFrameBits, nframes, scale, period, keep0, keep1,
-                               true, &pn);
-    if (rc != VD_OK) return rc;
-    return launch_frames_checked(d, rx_d, rx_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes, terminated,
-                                 scale, (hipStream_t)stream, &pn);
+    return launch_frames(d, frame_call({true, false, false, false}, rx_d, rx_stride, output_d, output_stride, frame_bits_d,
+                                       maxFrameBits, nframes, terminated ? 1 : 0, scale, period, keep0, keep1), stream);
 }
-
-// the host buffers laid out like the device ones (vd_run_frames): the last frame's part ends with the received
-// values of its maxFrameBits stages
 int vd_run_punct_frames(vd_decoder* d, const float* rx_h, size_t rx_stride, void* output_h, size_t output_stride,
                         const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int terminated, float scale, int period,
                         uint32_t keep0, uint32_t keep1, float* kernel_ms)
 {
-    Punct pn;
-    int rc = punct_frames_args(d, rx_h, rx_stride, output_h, output_stride, maxFrameBits, nframes, scale, period, keep0, keep1,
-                               false, &pn);
-    if (rc != VD_OK) return rc;
-    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
-    const size_t inB = (size_t)(nframes - 1) * rx_stride + pfrm_bytes(pn, (uint32_t)maxFrameBits);
-    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
-    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
-    VD_HIP(hipSetDevice(d->device));
-    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
-    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
-    if (rc != VD_OK) return rc;
-    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
-    if (inB) VD_HIP(hipMemcpyAsync(d->llr_d, rx_h, inB, hipMemcpyHostToDevice, d->stream));
-    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
-    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
-    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    rc = launch_frames_checked(d, (const float*)d->llr_d, rx_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes,
-                               terminated, scale, d->stream, &pn);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return VD_OK;
+    return run_frames(d, frame_call({true, false, false, false}, rx_h, rx_stride, output_h, output_stride, frame_bits_h,
+                                    maxFrameBits, nframes, terminated ? 1 : 0, scale, period, keep0, keep1), kernel_ms);
 }
 
-// ---- tail-biting frames (vd_frames.h "tail-biting frames"; vd_decode_tg<FRM+TB+...>, one frame per wave) ----
-// the argument checks of a tail-biting frame decode: VD_ERR_ARG (every format decodes: no VD_ERR_OPTIONS case)
-static int tb_frames_args(const vd_decoder* d, const void* llr, size_t llr_stride, const void* output, size_t output_stride,
-                          size_t maxFrameBits, int nframes, float scale, bool device)
-{
-    if (!d || !llr || !output) return fail(VD_ERR_ARG, "null argument");
-    if (const char* why = tb_args_error(device ? (uint64_t)(uintptr_t)llr : 0, llr_stride, output_stride, maxFrameBits, nframes,
-                                        scale))
-        return fail(VD_ERR_ARG, why);
-    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
-    return VD_OK;
-}
-
+// ---- tail-biting frames (vd_frames.h "tail-biting frames"; vd_decode_tg<FRM+TB+...>) ----
 int vd_run_device_tb_frames(vd_decoder* d, const float* llr_d, size_t llr_stride, void* output_d, size_t output_stride,
                             const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, float scale, void* stream)
 {
-    int rc = tb_frames_args(d, llr_d, llr_stride, output_d, output_stride, maxFrameBits, nframes, scale, true);
-    if (rc != VD_OK) return rc;
-    return launch_frames_checked(d, llr_d, llr_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes, 0, scale,
-                                 (hipStream_t)stream, nullptr, true);
+    return launch_frames(d, frame_call({false, true, false, false}, llr_d, llr_stride, output_d, output_stride, frame_bits_d,
+                                       maxFrameBits, nframes, kByteFramesTailbiting, scale), stream);
 }
-
-// the host buffers laid out like the device ones (vd_run_frames)
 int vd_run_tb_frames(vd_decoder* d, const float* llr_h, size_t llr_stride, void* output_h, size_t output_stride,
                      const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, float scale, float* kernel_ms)
 {
-    int rc = tb_frames_args(d, llr_h, llr_stride, output_h, output_stride, maxFrameBits, nframes, scale, false);
-    if (rc != VD_OK) return rc;
-    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
-    const size_t inB = (size_t)(nframes - 1) * llr_stride + 8 * maxFrameBits;
-    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
-    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
-    VD_HIP(hipSetDevice(d->device));
-    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB);
-    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
-    if (rc != VD_OK) return rc;
-    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
-    VD_HIP(hipMemcpyAsync(d->llr_d, llr_h, inB, hipMemcpyHostToDevice, d->stream));
-    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
-    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
-    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    rc = launch_frames_checked(d, (const float*)d->llr_d, llr_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes, 0,
-                               scale, d->stream, nullptr, true);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return VD_OK;
+    return run_frames(d, frame_call({false, true, false, false}, llr_h, llr_stride, output_h, output_stride, frame_bits_h,
+                                    maxFrameBits, nframes, kByteFramesTailbiting, scale), kernel_ms);
 }
 
 // ---- punctured tail-biting frames (vd_frames.h "punctured tail-biting frames"; vd_decode_tg<FRM+TB+PUN+...>) ----
-// the argument checks of a punctured tail-biting frame decode: VD_ERR_ARG / VD_ERR_OPTIONS, or *pn filled in
-static int punct_tb_frames_args(const vd_decoder* d, const void* rx, size_t rx_stride, const void* output, size_t output_stride,
-                                size_t maxFrameBits, int nframes, float scale, int period, uint32_t keep0, uint32_t keep1,
-                                bool device, Punct* pn)
-{
-    if (!d || !rx || !output) return fail(VD_ERR_ARG, "null argument");
-    if (const char* why = ptb_args_error(device ? (uint64_t)(uintptr_t)rx : 0, rx_stride, output_stride, maxFrameBits, nframes,
-                                         scale, period, keep0, keep1))
-        return fail(VD_ERR_ARG, why);
-    if (const char* why = frame_parts_error(maxFrameBits, nframes, d->partBits)) return fail(VD_ERR_ARG, why);
-    if (ch_of(d->options) == HARD)
-        return fail(VD_ERR_OPTIONS, "punctured tail-biting frames on a HARD decoder: a punctured value must decode as code 0 = "
-                                    "value 0, and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");
-    *pn = punct_make(period, keep0, keep1);
-    return VD_OK;
-}
-
 int vd_run_device_punct_tb_frames(vd_decoder* d, const float* rx_d, size_t rx_stride, void* output_d, size_t output_stride,
                                   const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, float scale, int period,
                                   uint32_t keep0, uint32_t keep1, void* stream)
 {
-    Punct pn;
-    int rc = punct_tb_frames_args(d, rx_d, rx_stride, output_d, output_stride, maxFrameBits, nframes, scale, period, keep0, keep1,
-                                  true, &pn);
-    if (rc != VD_OK) return rc;
-    return launch_frames_checked(d, rx_d, rx_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes, 0, scale,
-                                 (hipStream_t)stream, &pn, true);
+    return launch_frames(d, frame_call({true, true, false, false}, rx_d, rx_stride, output_d, output_stride, frame_bits_d,
+                                       maxFrameBits, nframes, kByteFramesTailbiting, scale, period, keep0, keep1), stream);
 }
-
-// the host buffers laid out like the device ones (vd_run_punct_frames): the last frame's part ends with the
-// received values of its maxFrameBits stages
 int vd_run_punct_tb_frames(vd_decoder* d, const float* rx_h, size_t rx_stride, void* output_h, size_t output_stride,
                            const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, float scale, int period,
                            uint32_t keep0, uint32_t keep1, float* kernel_ms)
 {
-    Punct pn;
-    int rc = punct_tb_frames_args(d, rx_h, rx_stride, output_h, output_stride, maxFrameBits, nframes, scale, period, keep0, keep1,
-                                  false, &pn);
-    if (rc != VD_OK) return rc;
-    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
-    const size_t inB = (size_t)(nframes - 1) * rx_stride + pfrm_bytes(pn, (uint32_t)maxFrameBits);
-    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
-    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
-    VD_HIP(hipSetDevice(d->device));
-    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
-    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
-    if (rc != VD_OK) return rc;
-    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
-    if (inB) VD_HIP(hipMemcpyAsync(d->llr_d, rx_h, inB, hipMemcpyHostToDevice, d->stream));
-    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
-    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
-    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    rc = launch_frames_checked(d, (const float*)d->llr_d, rx_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes, 0,
-                               scale, d->stream, &pn, true);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return VD_OK;
+    return run_frames(d, frame_call({true, true, false, false}, rx_h, rx_stride, output_h, output_stride, frame_bits_h,
+                                    maxFrameBits, nframes, kByteFramesTailbiting, scale, period, keep0, keep1), kernel_ms);
 }
 
 // ---- int8 frames (vd_frames.h "int8 frames"; vd_decode_tg<FRM+I8+...>, the byte twins of the four families) ----
-// the argument checks of an int8 frame decode: VD_ERR_ARG / VD_ERR_OPTIONS, or *pn filled in (null pattern: (1, 1, 1))
-static int byte_frames_args(const vd_decoder* d, const void* q, size_t q_stride, const void* output, size_t output_stride,
-                            size_t maxFrameBits, int nframes, int kind, float scale, int period, uint32_t keep0, uint32_t keep1,
-                            bool device, Punct* pn, bool* pun)
-{
-    if (!d || !q || !output) return fail(VD_ERR_ARG, "null argument");
-    if (const char* why = byte_frame_args_error(device ? (uint64_t)(uintptr_t)q : 0, q_stride, output_stride, maxFrameBits, nframes,
-                                                kind, scale, period, keep0, keep1, d->partBits))
-        return fail(VD_ERR_ARG, why);
-    *pun = !byte_frames_unpunctured(period, keep0, keep1);
-    const int ch = ch_of(d->options);
-    if (ch != HARD && ch != SOFT4 && ch != SOFT8)
-        return fail(VD_ERR_OPTIONS, "int8 frames on a SOFT16 or FP32 decoder: an int8 value carries nothing that a SOFT8 "
-                                    "decoder does not use; use HARD, SOFT4 or SOFT8");
-    if (ch == HARD && kind == kByteFramesOpen)
-        return fail(VD_ERR_OPTIONS, "open frames on a HARD decoder: the stages after an open frame are erasures, and HARD's "
-                                    "v > 0 ? 1 : 0 has no neutral code; terminate the frames or use SOFT4 or SOFT8");
-    if (ch == HARD && *pun)
-        return fail(VD_ERR_OPTIONS, "punctured frames on a HARD decoder: a punctured value must decode as code 0 = value 0, "
-                                    "and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4 or SOFT8");
-    *pn = punct_make(period, keep0, keep1);
-    return VD_OK;
-}
-
 int vd_run_device_byte_frames(vd_decoder* d, const int8_t* q_d, size_t q_stride, void* output_d, size_t output_stride,
                               const uint32_t* frame_bits_d, size_t maxFrameBits, int nframes, int kind, float scale,
                               int period, uint32_t keep0, uint32_t keep1, void* stream)
 {
-    Punct pn;
-    bool pun;
-    int rc = byte_frames_args(d, q_d, q_stride, output_d, output_stride, maxFrameBits, nframes, kind, scale, period, keep0,
-                              keep1, true, &pn, &pun);
-    if (rc != VD_OK) return rc;
-    return launch_frames_checked(d, q_d, q_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes,
-                                 kind == kByteFramesTerminated, scale, (hipStream_t)stream, pun ? &pn : nullptr,
-                                 kind == kByteFramesTailbiting, true);
+    return launch_frames(d, frame_call(byte_family(kind, period, keep0, keep1), q_d, q_stride, output_d, output_stride,
+                                       frame_bits_d, maxFrameBits, nframes, kind, scale, period, keep0, keep1), stream);
 }
-
-// the host buffers laid out like the device ones (vd_run_frames): the last frame's part ends with the bytes of its
-// maxFrameBits stages; the staging buffers are the decoder's, the lengths ride behind the bytes
 int vd_run_byte_frames(vd_decoder* d, const int8_t* q_h, size_t q_stride, void* output_h, size_t output_stride,
                        const uint32_t* frame_bits_h, size_t maxFrameBits, int nframes, int kind, float scale, int period,
                        uint32_t keep0, uint32_t keep1, float* kernel_ms)
 {
-    Punct pn;
-    bool pun;
-    int rc = byte_frames_args(d, q_h, q_stride, output_h, output_stride, maxFrameBits, nframes, kind, scale, period, keep0,
-                              keep1, false, &pn, &pun);
-    if (rc != VD_OK) return rc;
-    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
-    const size_t inB = (size_t)(nframes - 1) * q_stride + byte_pfrm_bytes(pn, (uint32_t)maxFrameBits);
-    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
-    const size_t lenOff = (inB + 15) & ~(size_t)15, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
-    VD_HIP(hipSetDevice(d->device));
-    rc = grow(d->llr_d, d->cap_llr, lenOff + lenB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
-    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
-    if (rc != VD_OK) return rc;
-    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
-    if (inB) VD_HIP(hipMemcpyAsync(d->llr_d, q_h, inB, hipMemcpyHostToDevice, d->stream));
-    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
-    // the words no frame writes (between the frames, of short and empty frames) keep the caller's values
-    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    rc = launch_frames_checked(d, d->llr_d, q_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes,
-                               kind == kByteFramesTerminated, scale, d->stream, pun ? &pn : nullptr,
-                               kind == kByteFramesTailbiting, true);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return VD_OK;
+    return run_frames(d, frame_call(byte_family(kind, period, keep0, keep1), q_h, q_stride, output_h, output_stride,
+                                    frame_bits_h, maxFrameBits, nframes, kind, scale, period, keep0, keep1), kernel_ms);
 }
 
 // ---- mixed frames (vd_frames.h "mixed frames"; vd_decode_tg<FRM+MIX+...>, one pattern and one place per frame) ----
@@ -997,119 +845,64 @@ int vd_frame_patterns(vd_decoder* d, uint32_t* triples, int* n)
     return VD_OK;
 }
 
-// the argument checks of a mixed frame decode: VD_ERR_ARG / VD_ERR_OPTIONS
-static int mixed_frames_args(const vd_decoder* d, const void* rx, size_t rx_stride, bool offsets, const void* output,
-                             size_t output_stride, size_t maxFrameBits, int nframes, int kind, float scale, bool i8, bool device)
+// a mixed call: a punctured family (float or int8, padded or tail-biting by the kind) with its two arrays
+static FrameCall mixed_call(bool i8, const void* rx, size_t rx_stride, const uint64_t* rx_offsets, void* output, size_t output_stride,
+                            const uint32_t* frame_bits, const uint8_t* rate, size_t maxFrameBits, int nframes, int kind, float scale)
 {
-    if (!d || !rx || !output) return fail(VD_ERR_ARG, "null argument");
-    const int ch = ch_of(d->options);
-    if (ch == HARD)
-        return fail(VD_ERR_OPTIONS, "mixed frames on a HARD decoder: a punctured value must decode as code 0 = value 0, and "
-                                    "HARD's v > 0 ? 1 : 0 turns it into a hard 0; use SOFT4, SOFT8, SOFT16 or FP32");
-    if (i8 && ch != SOFT4 && ch != SOFT8)
-        return fail(VD_ERR_OPTIONS, "int8 frames on a SOFT16 or FP32 decoder: an int8 value carries nothing that a SOFT8 "
-                                    "decoder does not use; use SOFT4 or SOFT8");
-    if (const char* why = mixed_args_error(device ? (uint64_t)(uintptr_t)rx : 0, rx_stride, offsets, output_stride, maxFrameBits,
-                                           nframes, kind, scale, d->mixTab, d->mixN, i8 ? 1u : 4u, d->partBits))
-        return fail(VD_ERR_ARG, why);
-    return VD_OK;
-}
-
-static int run_device_mixed(vd_decoder* d, const void* rx_d, size_t rx_stride, const uint64_t* rx_offsets_d, void* output_d,
-                            size_t output_stride, const uint32_t* frame_bits_d, const uint8_t* rate_d, size_t maxFrameBits,
-                            int nframes, int kind, float scale, hipStream_t s, bool i8)
-{
-    int rc = mixed_frames_args(d, rx_d, rx_stride, rx_offsets_d != nullptr, output_d, output_stride, maxFrameBits, nframes, kind,
-                               scale, i8, true);
-    if (rc != VD_OK) return rc;
-    const MixArgs mix = {rate_d, rx_offsets_d};
-    return launch_frames_checked(d, rx_d, rx_stride, output_d, output_stride, frame_bits_d, maxFrameBits, nframes,
-                                 kind == kByteFramesTerminated, scale, s, nullptr, kind == kByteFramesTailbiting, i8, &mix);
+    FrameCall c = frame_call({true, kind == kByteFramesTailbiting, i8, true}, rx, rx_stride, output, output_stride, frame_bits,
+                             maxFrameBits, nframes, kind, scale);
+    c.rate = rate;
+    c.off = rx_offsets;
+    return c;
 }
 
 int vd_run_device_mixed_frames(vd_decoder* d, const float* rx_d, size_t rx_stride, const uint64_t* rx_offsets_d, void* output_d,
                                size_t output_stride, const uint32_t* frame_bits_d, const uint8_t* rate_d, size_t maxFrameBits,
                                int nframes, int kind, float scale, void* stream)
 {
-    return run_device_mixed(d, rx_d, rx_stride, rx_offsets_d, output_d, output_stride, frame_bits_d, rate_d, maxFrameBits, nframes,
-                            kind, scale, (hipStream_t)stream, false);
+    return launch_frames(d, mixed_call(false, rx_d, rx_stride, rx_offsets_d, output_d, output_stride, frame_bits_d, rate_d,
+                                       maxFrameBits, nframes, kind, scale), stream);
 }
 int vd_run_device_byte_mixed_frames(vd_decoder* d, const int8_t* q_d, size_t q_stride, const uint64_t* q_offsets_d, void* output_d,
                                     size_t output_stride, const uint32_t* frame_bits_d, const uint8_t* rate_d, size_t maxFrameBits,
                                     int nframes, int kind, float scale, void* stream)
 {
-    return run_device_mixed(d, q_d, q_stride, q_offsets_d, output_d, output_stride, frame_bits_d, rate_d, maxFrameBits, nframes,
-                            kind, scale, (hipStream_t)stream, true);
+    return launch_frames(d, mixed_call(true, q_d, q_stride, q_offsets_d, output_d, output_stride, frame_bits_d, rate_d,
+                                       maxFrameBits, nframes, kind, scale), stream);
 }
 
-// the host buffers laid out like the device ones (vd_run_frames).  Without offsets the last frame's part ends with the
-// received values of a maxFrameBits frame under the table's densest pattern; with offsets the buffer holds rx_total
-// values and every frame must lie inside it (checked here, where the arrays are at hand).  The staging buffers are the
-// decoder's: the offsets, the lengths and the rate indices ride behind the values.
-static int run_mixed(vd_decoder* d, const void* rx_h, size_t rx_stride, const uint64_t* rx_offsets_h, size_t rx_total,
-                     void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h, size_t maxFrameBits,
-                     int nframes, int kind, float scale, float* kernel_ms, bool i8)
+// The blocking mixed variants know every frame's place: with offsets the buffer holds rx_total values and every frame
+// must lie inside it (checked here, where the arrays are at hand).
+static int run_mixed(vd_decoder* d, FrameCall c, size_t rx_total, float* kernel_ms)
 {
-    int rc = mixed_frames_args(d, rx_h, rx_stride, rx_offsets_h != nullptr, output_h, output_stride, maxFrameBits, nframes, kind,
-                               scale, i8, false);
+    const int rc = check_frames(d, c, false);
     if (rc != VD_OK) return rc;
-    const size_t vb = i8 ? 1 : 4;
-    if (rx_offsets_h) {
+    if (c.off) {
         if (rx_total > ((size_t)1 << 40)) return fail(VD_ERR_ARG, "rx_total above 2^40 values");
-        for (int f = 0; f < nframes; f++) {
-            const uint32_t ri = rate_h ? rate_h[f] : 0u;
-            const uint32_t S = frame_bits_h && frame_bits_h[f] < maxFrameBits ? frame_bits_h[f] : (uint32_t)maxFrameBits;
+        for (int f = 0; f < c.a.nframes; f++) {
+            const uint32_t ri = c.rate ? c.rate[f] : 0u;
+            const uint32_t S = c.bits && c.bits[f] < c.a.maxFrameBits ? c.bits[f] : (uint32_t)c.a.maxFrameBits;
             if (ri >= (uint32_t)d->mixN || S == 0) continue;  // (reads nothing)
-            if (!mixed_frame_inside(rx_offsets_h[f], pfrm_bytes<1>(d->mixTab[ri].pn, S), rx_total))
+            if (!mixed_frame_inside(c.off[f], pfrm_bytes<1>(d->mixTab[ri].pn, S), rx_total))
                 return fail(VD_ERR_ARG, "frame " + std::to_string(f) + " does not lie inside the rx_total values of the buffer");
         }
     }
-    const size_t outW = vd_frame_output_size(d->options, maxFrameBits);
-    const size_t lastB = i8 ? mix_max_bytes<1>(d->mixTab, d->mixN, (uint32_t)maxFrameBits)
-                            : mix_max_bytes<4>(d->mixTab, d->mixN, (uint32_t)maxFrameBits);
-    const size_t inB = rx_offsets_h ? rx_total * vb : (size_t)(nframes - 1) * rx_stride + lastB;
-    const size_t outB = (size_t)(nframes - 1) * output_stride + outW;
-    const size_t offOff = (inB + 15) & ~(size_t)15, offB = rx_offsets_h ? (size_t)nframes * 8 : 0;
-    const size_t lenOff = offOff + offB, lenB = frame_bits_h ? (size_t)nframes * 4 : 0;
-    const size_t rateOff = lenOff + lenB, rateB = rate_h ? (size_t)nframes : 0;
-    VD_HIP(hipSetDevice(d->device));
-    rc = grow(d->llr_d, d->cap_llr, rateOff + rateB + 16);  // (+ 16: a buffer even when no frame holds a kept value)
-    if (rc == VD_OK) rc = grow(d->out_d, d->cap_out, outB + 16);
-    if (rc != VD_OK) return rc;
-    uint64_t* const off_d = rx_offsets_h ? (uint64_t*)((char*)d->llr_d + offOff) : nullptr;
-    uint32_t* const len_d = frame_bits_h ? (uint32_t*)((char*)d->llr_d + lenOff) : nullptr;
-    uint8_t* const rate_d = rate_h ? (uint8_t*)d->llr_d + rateOff : nullptr;
-    if (inB) VD_HIP(hipMemcpyAsync(d->llr_d, rx_h, inB, hipMemcpyHostToDevice, d->stream));
-    if (off_d) VD_HIP(hipMemcpyAsync(off_d, rx_offsets_h, offB, hipMemcpyHostToDevice, d->stream));
-    if (len_d) VD_HIP(hipMemcpyAsync(len_d, frame_bits_h, lenB, hipMemcpyHostToDevice, d->stream));
-    if (rate_d) VD_HIP(hipMemcpyAsync(rate_d, rate_h, rateB, hipMemcpyHostToDevice, d->stream));
-    // the words no frame writes (between the frames, of short, empty and out-of-table frames) keep the caller's values
-    VD_HIP(hipMemcpyAsync(d->out_d, output_h, outB, hipMemcpyHostToDevice, d->stream));
-    VD_HIP(hipEventRecord(d->ev0, d->stream));
-    const MixArgs mix = {rate_d, off_d};
-    rc = launch_frames_checked(d, d->llr_d, rx_stride, d->out_d, output_stride, len_d, maxFrameBits, nframes,
-                               kind == kByteFramesTerminated, scale, d->stream, nullptr, kind == kByteFramesTailbiting, i8, &mix);
-    if (rc != VD_OK) return rc;
-    VD_HIP(hipEventRecord(d->ev1, d->stream));
-    VD_HIP(hipMemcpyAsync(output_h, d->out_d, outB, hipMemcpyDeviceToHost, d->stream));
-    VD_HIP(hipStreamSynchronize(d->stream));
-    if (kernel_ms) VD_HIP(hipEventElapsedTime(kernel_ms, d->ev0, d->ev1));
-    return VD_OK;
+    return run_frames_staged(d, c, rx_total, kernel_ms);
 }
 
 int vd_run_mixed_frames(vd_decoder* d, const float* rx_h, size_t rx_stride, const uint64_t* rx_offsets_h, size_t rx_total,
                         void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h,
                         size_t maxFrameBits, int nframes, int kind, float scale, float* kernel_ms)
 {
-    return run_mixed(d, rx_h, rx_stride, rx_offsets_h, rx_total, output_h, output_stride, frame_bits_h, rate_h, maxFrameBits,
-                     nframes, kind, scale, kernel_ms, false);
+    return run_mixed(d, mixed_call(false, rx_h, rx_stride, rx_offsets_h, output_h, output_stride, frame_bits_h, rate_h,
+                                   maxFrameBits, nframes, kind, scale), rx_total, kernel_ms);
 }
 int vd_run_byte_mixed_frames(vd_decoder* d, const int8_t* q_h, size_t q_stride, const uint64_t* q_offsets_h, size_t q_total,
                              void* output_h, size_t output_stride, const uint32_t* frame_bits_h, const uint8_t* rate_h,
                              size_t maxFrameBits, int nframes, int kind, float scale, float* kernel_ms)
 {
-    return run_mixed(d, q_h, q_stride, q_offsets_h, q_total, output_h, output_stride, frame_bits_h, rate_h, maxFrameBits, nframes,
-                     kind, scale, kernel_ms, true);
+    return run_mixed(d, mixed_call(true, q_h, q_stride, q_offsets_h, output_h, output_stride, frame_bits_h, rate_h,
+                                   maxFrameBits, nframes, kind, scale), q_total, kernel_ms);
 }
 
 void* vd_host_alloc(size_t bytes)

@@ -69,23 +69,6 @@ inline bool frame_pad(float scale, float* pad)
     return true;
 }
 
-// The argument checks of vd_run_device_frames (all VD_ERR_ARG): the message, or null when the arguments are good.
-// llr_addr: the address of the first frame's first float.
-inline const char* frame_args_error(uint64_t llr_addr, uint64_t llr_stride, uint64_t output_stride, uint64_t maxFrameBits,
-                                    int nframes, float scale)
-{
-    float pad;
-    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
-    if (nframes < 1) return "nframes must be >= 1";
-    if (!frame_pad(scale, &pad)) return "scale must be finite and > 0 (and -65536 / scale finite)";
-    if (llr_addr & 7) return "llr_d must be 8-byte aligned";
-    if ((llr_stride & 7) || (output_stride & 3)) return "llr_stride % 8 or output_stride % 4 != 0";
-    if (nframes > 1 && llr_stride < 8 * maxFrameBits) return "llr_stride smaller than 8 * maxFrameBits: frames would overlap";
-    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
-        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
-    return nullptr;
-}
-
 // ---------------------------------------------------------------- punctured frames (channel ids kFrm + kPun + format)
 // A punctured frame of S stages under a pattern (vd_punct.h) holds the punct_len(2 S) kept values of its 2 S
 // mother-code values, the pattern's phase restarting at the frame's first stage: frame stage t uses bit
@@ -144,25 +127,6 @@ VD_FRAMES_HD PfrmOff pfrm_offsets(const Punct& pn, uint32_t base4, uint32_t r0, 
     const uint32_t has0 = (pn.keep0 >> r) & 1u, has1 = (pn.keep1 >> r) & 1u;
     const uint32_t b = base4 + pfrm_mul24(dq, VB * pn.kp) + punct_before(pn, r) * VB;
     return {b | ((has0 ^ 1u) * kFrmOutside) | before, (b + has0 * VB) | ((has1 ^ 1u) * kFrmOutside) | before};
-}
-
-// The argument checks of vd_run_device_punct_frames (all VD_ERR_ARG): the message, or null when the arguments are
-// good.  rx_addr: the address of the first frame's first float; maxFrameBits counts stages.
-inline const char* pfrm_args_error(uint64_t rx_addr, uint64_t rx_stride, uint64_t output_stride, uint64_t maxFrameBits,
-                                   int nframes, float scale, int period, uint32_t keep0, uint32_t keep1)
-{
-    float pad;
-    if (!punct_valid(period, keep0, keep1))
-        return "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
-    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
-    if (nframes < 1) return "nframes must be >= 1";
-    if (!frame_pad(scale, &pad)) return "scale must be finite and > 0 (and -65536 / scale finite)";
-    if ((rx_addr | rx_stride | output_stride) & 3) return "rx_d, rx_stride and output_stride must be multiples of 4 bytes";
-    if (nframes > 1 && rx_stride < pfrm_bytes(punct_make(period, keep0, keep1), (uint32_t)maxFrameBits))
-        return "rx_stride smaller than 4 * vd_punctured_len(2 * maxFrameBits): frames would overlap";
-    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
-        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
-    return nullptr;
 }
 
 // ---------------------------------------------------------------- tail-biting frames (channel ids kFrm + kTb + format)
@@ -238,22 +202,6 @@ VD_FRAMES_HD uint32_t tb_stage_offset(uint32_t g0, uint32_t s, uint32_t S, const
     return tb_offset<VB>(tb_lane_stage(tb_group_r0(g0, S, rc.m32), s, S, rc.m16));
 }
 
-// The argument checks of vd_run_device_tb_frames (all VD_ERR_ARG): the message, or null when the arguments are
-// good; frame_args_error's rules (no pad value to form: the scale only has to be finite and > 0).
-inline const char* tb_args_error(uint64_t llr_addr, uint64_t llr_stride, uint64_t output_stride, uint64_t maxFrameBits,
-                                 int nframes, float scale)
-{
-    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
-    if (nframes < 1) return "nframes must be >= 1";
-    if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
-    if (llr_addr & 7) return "llr_d must be 8-byte aligned";
-    if ((llr_stride & 7) || (output_stride & 3)) return "llr_stride % 8 or output_stride % 4 != 0";
-    if (nframes > 1 && llr_stride < 8 * maxFrameBits) return "llr_stride smaller than 8 * maxFrameBits: frames would overlap";
-    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
-        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
-    return nullptr;
-}
-
 // ---------------------------------------------------------------- punctured tail-biting frames (channel ids kFrm + kTb + kPun + format)
 // A punctured tail-biting frame of S >= 1 stages under a pattern holds the punct_len(2 S) kept values of its 2 S
 // mother-code values, and the pattern's phase belongs to the frame stage: stage p of the extended stream is frame
@@ -325,24 +273,6 @@ template <uint32_t VB = 4>
 VD_FRAMES_HD PfrmOff ptb_stage_offsets(const Punct& pn, uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
 {
     return ptb_offsets<VB>(pn, ptb_group<VB>(pn, g0, S, rc), s, S, rc.m16);
-}
-
-// The argument checks of vd_run_device_punct_tb_frames (all VD_ERR_ARG): the message, or null when the arguments
-// are good; pfrm_args_error's rules with tb_args_error's scale rule (no pad value to form).
-inline const char* ptb_args_error(uint64_t rx_addr, uint64_t rx_stride, uint64_t output_stride, uint64_t maxFrameBits,
-                                  int nframes, float scale, int period, uint32_t keep0, uint32_t keep1)
-{
-    if (!punct_valid(period, keep0, keep1))
-        return "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
-    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
-    if (nframes < 1) return "nframes must be >= 1";
-    if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
-    if ((rx_addr | rx_stride | output_stride) & 3) return "rx_d, rx_stride and output_stride must be multiples of 4 bytes";
-    if (nframes > 1 && rx_stride < pfrm_bytes(punct_make(period, keep0, keep1), (uint32_t)maxFrameBits))
-        return "rx_stride smaller than 4 * vd_punctured_len(2 * maxFrameBits): frames would overlap";
-    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
-        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
-    return nullptr;
 }
 
 // ---------------------------------------------------------------- frames in parts (all four families)
@@ -424,12 +354,12 @@ inline const char* frame_parts_error(uint64_t maxFrameBits, int nframes, uint64_
 // its decode is the float family's decode of the frame (float)q -- the same padded or extended stream, pad value,
 // erasures, phase rule and parts.  Only the byte offsets differ, the helpers above with VB = 1:
 //   unpunctured (pattern (1, 1, 1)): a stage's two values are one aligned 16-bit access (first encoder output in
-//     the low byte) against a resource of 2 S bytes.  Stage p of the padded stream reads at byte_frame_offset(p) =
+//     the low byte) against a resource of 2 S bytes.  Stage p of the padded stream reads at frame_offset<1>(p) =
 //     2 (p - 26) with frame_offset's clamp: it wraps to 2^32 - 2 (26 - p) for p < 26, and for p = 25 the end of the
 //     2-byte access, 2^32, is 0 in 32 bits as the end of the 8-byte access is, so such a lane reads at kFrmOutside,
 //     whose end 2^31 + 2 lies past every range (<= 2 kFrmMaxBits) with no wrap.  For p >= 26, 2 p < 2^22.  A
-//     tail-biting frame stage t reads at byte_tb_offset(t) = 2 t, offset + 2 <= 2 S;
-//   punctured: single-byte accesses against a resource of byte_pfrm_bytes = punct_len(2 S) <= 2^21 bytes, at the
+//     tail-biting frame stage t reads at tb_offset<1>(t) = 2 t, offset + 2 <= 2 S;
+//   punctured: single-byte accesses against a resource of pfrm_bytes<1> = punct_len(2 S) <= 2^21 bytes, at the
 //     kept index itself.  The offsets are a quarter of the float ones, so what the float maps rely on holds with
 //     room to spare: base4 = q0 Kp <= 2 S < 2^22 and every kept offset stay below 2^24 (the 24-bit products x m16 <
 //     2^23, dq Kp < 112 * 32, dq period < 112 * 16 are those of pfrm_offsets, VB = 1 only drops a factor), a
@@ -439,55 +369,11 @@ inline const char* frame_parts_error(uint64_t maxFrameBits, int nframes, uint64_
 // it on the device (frames of one stage, neighbours of other frames' extreme values).
 // tests/cxx/byte_frames_check.cpp checks the helpers below against a plain enumeration.
 constexpr int kByteFramesOpen = 0, kByteFramesTerminated = 1, kByteFramesTailbiting = 2;  // vd_capi.h VD_FRAMES_*
-VD_FRAMES_HD uint32_t byte_frame_offset(uint32_t p) { return frame_offset<1>(p); }
-VD_FRAMES_HD uint32_t byte_tb_offset(uint32_t t) { return tb_offset<1>(t); }
-VD_FRAMES_HD uint32_t byte_tb_stage_offset(uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
-{
-    return tb_stage_offset<1>(g0, s, S, rc);
-}
-VD_FRAMES_HD uint32_t byte_pfrm_bytes(const Punct& pn, uint32_t S) { return pfrm_bytes<1>(pn, S); }
-VD_FRAMES_HD uint32_t byte_pfrm_base(const Punct& pn, uint32_t t0, uint32_t* r0) { return pfrm_base<1>(pn, t0, r0); }
-VD_FRAMES_HD PfrmOff byte_pfrm_offsets(const Punct& pn, uint32_t base1, uint32_t r0, uint32_t lead, uint32_t s)
-{
-    return pfrm_offsets<1>(pn, base1, r0, lead, s);
-}
-VD_FRAMES_HD PfrmOff byte_ptb_stage_offsets(const Punct& pn, uint32_t g0, uint32_t s, uint32_t S, const TbRecip& rc)
-{
-    return ptb_stage_offsets<1>(pn, g0, s, S, rc);
-}
 // the pattern that selects the unpunctured kernels (any other valid pattern, a keep-all one of a longer period
 // too, selects the punctured ones)
 VD_FRAMES_HD bool byte_frames_unpunctured(int period, uint32_t keep0, uint32_t keep1)
 {
     return period == 1 && keep0 == 1u && keep1 == 1u;
-}
-
-// The argument checks of vd_run_device_byte_frames (all VD_ERR_ARG): the message, or null when the arguments are
-// good.  q_addr: the address of the first frame's first byte; partBits: the decoder's part length.
-inline const char* byte_frame_args_error(uint64_t q_addr, uint64_t q_stride, uint64_t output_stride, uint64_t maxFrameBits,
-                                         int nframes, int kind, float scale, int period, uint32_t keep0, uint32_t keep1,
-                                         uint64_t partBits)
-{
-    float pad;
-    if (kind != kByteFramesOpen && kind != kByteFramesTerminated && kind != kByteFramesTailbiting)
-        return "kind must be VD_FRAMES_OPEN, VD_FRAMES_TERMINATED or VD_FRAMES_TAILBITING";
-    if (!punct_valid(period, keep0, keep1))
-        return "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
-    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
-    if (nframes < 1) return "nframes must be >= 1";
-    if (kind == kByteFramesTailbiting) {
-        if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
-    } else if (!frame_pad(scale, &pad)) {
-        return "scale must be finite and > 0 (and -65536 / scale finite)";
-    }
-    if (byte_frames_unpunctured(period, keep0, keep1) && ((q_addr | q_stride) & 1))
-        return "q_d and q_stride must be multiples of 2 bytes under pattern (1, 1, 1): a stage is one 16-bit access";
-    if (output_stride & 3) return "output_stride must be a multiple of 4 bytes";
-    if (nframes > 1 && q_stride < byte_pfrm_bytes(punct_make(period, keep0, keep1), (uint32_t)maxFrameBits))
-        return "q_stride smaller than vd_punctured_len(2 * maxFrameBits): frames would overlap";
-    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
-        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
-    return frame_parts_error(maxFrameBits, nframes, partBits);
 }
 
 // ---------------------------------------------------------------- mixed frames (channel ids kMix + a punctured frame id)
@@ -538,35 +424,124 @@ inline uint32_t mix_max_bytes(const MixRecord* table, int n, uint32_t S)
     }
     return m;
 }
-// The argument checks of vd_run_device_mixed_frames (vb = 4) and vd_run_device_byte_mixed_frames (vb = 1), all
-// VD_ERR_ARG: the message, or null when the arguments are good.  rx_addr: the address the offsets or strides count
-// from; offsets: the launch has per-frame offsets (rx_stride is then ignored); table, n: the decoder's patterns.
-inline const char* mixed_args_error(uint64_t rx_addr, uint64_t rx_stride, bool offsets, uint64_t output_stride, uint64_t maxFrameBits,
-                                    int nframes, int kind, float scale, const MixRecord* table, int n, uint32_t vb, uint64_t partBits)
-{
-    float pad;
-    if (n < 1 || n > kMixMaxPatterns || !table) return "the decoder's pattern table is empty: call vd_set_frame_patterns first";
-    if (kind != kByteFramesOpen && kind != kByteFramesTerminated && kind != kByteFramesTailbiting)
-        return "kind must be VD_FRAMES_OPEN, VD_FRAMES_TERMINATED or VD_FRAMES_TAILBITING";
-    if (maxFrameBits < 1 || maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
-    if (nframes < 1) return "nframes must be >= 1";
-    if (kind == kByteFramesTailbiting) {
-        if (!(scale > 0.0f) || !(scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
-    } else if (!frame_pad(scale, &pad)) {
-        return "scale must be finite and > 0 (and -65536 / scale finite)";
-    }
-    if (vb == 4 && (rx_addr & 3)) return "rx_d must be 4-byte aligned";
-    if (vb == 4 && !offsets && (rx_stride & 3)) return "rx_stride must be a multiple of 4 bytes";
-    if (output_stride & 3) return "output_stride must be a multiple of 4 bytes";
-    if (nframes > 1 && !offsets &&
-        rx_stride < (vb == 4 ? mix_max_bytes<4>(table, n, (uint32_t)maxFrameBits) : mix_max_bytes<1>(table, n, (uint32_t)maxFrameBits)))
-        return "rx_stride smaller than the received bytes of a maxFrameBits frame under the table's densest pattern: frames would overlap";
-    if (nframes > 1 && output_stride < 4ull * frame_words((uint32_t)maxFrameBits))
-        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
-    return frame_parts_error(maxFrameBits, nframes, partBits);
-}
 // The blocking host variants know every frame's place: frame f (S stages, pattern index rate, out-of-table or S = 0:
 // nothing read) must lie inside the total values of the buffer.  first .. first + count: the values it reads.
 inline bool mixed_frame_inside(uint64_t first, uint64_t count, uint64_t total) { return count <= total && first <= total - count; }
+
+// ---------------------------------------------------------------- the family record and the one argument check
+// What a frame launch is, in four bits: pun, the frames hold the kept values of punctured frames; tb, they are
+// tail-biting (no pad: terminated means nothing); i8, they hold int8 values and strides count bytes; mix, every frame
+// has its own pattern of the decoder's table (always a punctured kernel: pun is set with it).  The kernel table
+// (vd_plan.h launcher_frames), the names (plan_name), the argument check below and the launch (vd_capi.hip) all go
+// by this record.
+struct FrameFamily {
+    bool pun, tb, i8, mix;
+};
+// the family of vd_decoder_kernel_name's input codes 3 .. 14: 3 .. 6 the float families (frames, punctured,
+// tail-biting, punctured tail-biting), 7 .. 10 their int8 twins, 11 / 12 mixed frames padded / tail-biting, 13 / 14
+// their int8 twins
+inline FrameFamily frame_family_of_input(int llr)
+{
+    if (llr >= 11) return {true, (llr & 1) == 0, llr >= 13, true};
+    return {((llr - 3) & 1) != 0, ((llr - 3) & 2) != 0, llr >= 7, false};
+}
+
+constexpr int kFrameErrOptions = -1, kFrameErrArg = -2;  // vd_capi.h VD_ERR_OPTIONS, VD_ERR_ARG
+constexpr int kFrameHard = 0, kFrameSoft8 = 2;           // vd_kernels.h HARD, SOFT8 (the format: options & 0xF)
+
+// One call of a frame entry point, as plain values.
+struct FrameArgs {
+    FrameFamily fam;            // int8 frames: pun = !byte_frames_unpunctured(pattern); tb = kind is tail-biting
+    uint64_t addr;              // of the first frame's first value; 0 for the host buffers of the blocking variants
+    uint64_t stride;            // bytes from a frame's values to the next frame's
+    bool offsets;               // mixed: the launch has per-frame offsets (the stride is then ignored)
+    uint64_t outStride;
+    uint64_t maxFrameBits;      // in stages
+    int nframes;
+    int kind;                   // kByteFrames*
+    float scale;
+    int period;                 // the pattern; (1, 1, 1) for frames and tail-biting frames, unused by mixed launches
+    uint32_t keep0, keep1;
+    int options;                // the decoder's: its format decides the refusals
+    uint64_t partBits;          // ... its part length
+    const MixRecord* table;     // ... and its pattern table (mixed launches)
+    int tableN;
+};
+// the bytes the values of a frame of S <= kFrmMaxBits stages occupy at most: under the call's (valid) pattern, or
+// under the table's densest one
+inline uint32_t frame_value_bytes(const FrameArgs& a, uint32_t S)
+{
+    if (a.fam.mix) return a.fam.i8 ? mix_max_bytes<1>(a.table, a.tableN, S) : mix_max_bytes<4>(a.table, a.tableN, S);
+    const Punct pn = punct_make(a.period, a.keep0, a.keep1);
+    return a.fam.i8 ? pfrm_bytes<1>(pn, S) : pfrm_bytes<4>(pn, S);
+}
+
+#define VD_HARD_PUNCTURED " on a HARD decoder: a punctured value must decode as code 0 = value 0, and HARD's v > 0 ? 1 : 0 turns it into a hard 0; use "
+#define VD_HARD_OPEN "open frames on a HARD decoder: the stages after an open frame are erasures, and HARD's v > 0 ? 1 : 0 has no neutral code; terminate the frames or use "
+#define VD_I8_WIDE "int8 frames on a SOFT16 or FP32 decoder: an int8 value carries nothing that a SOFT8 decoder does not use; use "
+// The checks of every frame entry point behind its null-pointer check: the message and *code (kFrameErrArg or
+// kFrameErrOptions), or null when the call is good.  One order for all: the argument rules (kind, pattern, maxFrameBits,
+// nframes, scale, alignment, overlap of the values, overlap of the output), then frame_parts_error, then the refusals
+// by the decoder's format (int8 on SOFT16 / FP32, open frames on HARD, punctured frames on HARD; none for tail-biting
+// frames).  Mixed launches differ: their refusals come first and the empty table leads their argument rules.  The
+// alignment rule, the overlap rule's frame bytes and the wording are the family's.
+inline const char* frame_args_error(const FrameArgs& a, int* code)
+{
+    const FrameFamily f = a.fam;
+    const int ch = a.options & 0xF;
+    float pad;
+    *code = kFrameErrOptions;
+    if (f.mix && ch == kFrameHard) return "mixed frames" VD_HARD_PUNCTURED "SOFT4, SOFT8, SOFT16 or FP32";
+    if (f.mix && f.i8 && ch > kFrameSoft8) return VD_I8_WIDE "SOFT4 or SOFT8";
+    *code = kFrameErrArg;
+    if (f.mix && (a.tableN < 1 || a.tableN > kMixMaxPatterns || !a.table))
+        return "the decoder's pattern table is empty: call vd_set_frame_patterns first";
+    if ((f.i8 || f.mix) && a.kind != kByteFramesOpen && a.kind != kByteFramesTerminated && a.kind != kByteFramesTailbiting)
+        return "kind must be VD_FRAMES_OPEN, VD_FRAMES_TERMINATED or VD_FRAMES_TAILBITING";
+    if (!f.mix && !punct_valid(a.period, a.keep0, a.keep1))
+        return "invalid puncture pattern: 1 <= period <= 16, keep0 and keep1 are period-bit masks, at least one bit set";
+    if (a.maxFrameBits < 1 || a.maxFrameBits > kFrmMaxBits) return "maxFrameBits must be in [1, 2^20]";
+    if (a.nframes < 1) return "nframes must be >= 1";
+    if (f.tb) {  // no pad value to form
+        if (!(a.scale > 0.0f) || !(a.scale <= 3.4028234663852886e38f)) return "scale must be finite and > 0";
+    } else if (!frame_pad(a.scale, &pad)) {
+        return "scale must be finite and > 0 (and -65536 / scale finite)";
+    }
+    // alignment: of the widest access a stage's values take
+    if (f.mix) {  // single values, at offsets that count values
+        if (!f.i8 && (a.addr & 3)) return "rx_d must be 4-byte aligned";
+        if (!f.i8 && !a.offsets && (a.stride & 3)) return "rx_stride must be a multiple of 4 bytes";
+    } else if (f.i8) {
+        if (!f.pun && ((a.addr | a.stride) & 1))
+            return "q_d and q_stride must be multiples of 2 bytes under pattern (1, 1, 1): a stage is one 16-bit access";
+    } else if (f.pun) {
+        if ((a.addr | a.stride | a.outStride) & 3) return "rx_d, rx_stride and output_stride must be multiples of 4 bytes";
+    } else {
+        if (a.addr & 7) return "llr_d must be 8-byte aligned";
+        if ((a.stride & 7) || (a.outStride & 3)) return "llr_stride % 8 or output_stride % 4 != 0";
+    }
+    if ((f.i8 || f.mix) && (a.outStride & 3)) return "output_stride must be a multiple of 4 bytes";
+    if (a.nframes > 1 && !(f.mix && a.offsets) && a.stride < frame_value_bytes(a, (uint32_t)a.maxFrameBits))
+        return f.mix   ? "rx_stride smaller than the received bytes of a maxFrameBits frame under the table's densest pattern: frames would overlap"
+               : f.i8  ? "q_stride smaller than vd_punctured_len(2 * maxFrameBits): frames would overlap"
+               : f.pun ? "rx_stride smaller than 4 * vd_punctured_len(2 * maxFrameBits): frames would overlap"
+                       : "llr_stride smaller than 8 * maxFrameBits: frames would overlap";
+    if (a.nframes > 1 && a.outStride < 4ull * frame_words((uint32_t)a.maxFrameBits))
+        return "output_stride smaller than vd_frame_output_size(maxFrameBits): frames would overlap";
+    if (const char* why = frame_parts_error(a.maxFrameBits, a.nframes, a.partBits)) return why;
+    if (f.mix) return nullptr;
+    *code = kFrameErrOptions;
+    if (f.i8 && ch > kFrameSoft8) return VD_I8_WIDE "HARD, SOFT4 or SOFT8";
+    if (ch == kFrameHard && a.kind == kByteFramesOpen && (f.i8 || !f.pun))
+        return f.i8 ? VD_HARD_OPEN "SOFT4 or SOFT8" : VD_HARD_OPEN "SOFT4, SOFT8, SOFT16 or FP32";
+    if (ch == kFrameHard && f.pun)
+        return f.i8   ? "punctured frames" VD_HARD_PUNCTURED "SOFT4 or SOFT8"
+               : f.tb ? "punctured tail-biting frames" VD_HARD_PUNCTURED "SOFT4, SOFT8, SOFT16 or FP32"
+                      : "punctured frames" VD_HARD_PUNCTURED "SOFT4, SOFT8, SOFT16 or FP32";
+    return nullptr;
+}
+#undef VD_HARD_PUNCTURED
+#undef VD_HARD_OPEN
+#undef VD_I8_WIDE
 
 }  // namespace vd

@@ -140,164 +140,48 @@ typename L::fn launcher_punct(int ch, int me, bool o16)
     return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
 }
 
-// Frame launches (channel ids kFrm + format, vd_kernel_tg.h; vd_frames.h): vd_decode_tg only, all 12 pairs x
-// {O32, O16} (HARD too: a terminated frame needs no neutral code), again in a table of their own.
-template <class L>
-typename L::fn launcher_frames(int ch, int me, bool o16)
-{
-    struct Table {
-        typename L::fn at[5][3][2] = {};
-        Table()
-        {
-#define VD_X(C, M)                                      \
-    at[C][M][0] = &L::template tg<kFrm + C, M, 32>;     \
-    at[C][M][1] = &L::template tg<kFrm + C, M, 16>;
-            VD_TG_PAIRS(VD_X)
-#undef VD_X
-        }
-    };
-    static const Table t;
-    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
-}
-
-// Punctured frames (channel ids kFrm + kPun + format, vd_kernel_tg.h; vd_frames.h): the frame launch of the
-// punctured pairs, 9 pairs x {O32, O16}, planned by plan_frames like every frame launch.
-template <class L>
-typename L::fn launcher_punct_frames(int ch, int me, bool o16)
-{
-    struct Table {
-        typename L::fn at[5][3][2] = {};
-        Table()
-        {
-#define VD_X(C, M)                                             \
-    at[C][M][0] = &L::template tg<kFrm + kPun + C, M, 32>;     \
-    at[C][M][1] = &L::template tg<kFrm + kPun + C, M, 16>;
-            VD_PUN_PAIRS(VD_X)
-#undef VD_X
-        }
-    };
-    static const Table t;
-    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
-}
-
-// Tail-biting frames (channel ids kFrm + kTb + format, vd_kernel_tg.h; vd_frames.h): the frame launch with the
-// wrap-around in its loads, all 12 pairs x {O32, O16} (no pad, no erasure: HARD too), planned by plan_frames.
-template <class L>
-typename L::fn launcher_tb_frames(int ch, int me, bool o16)
-{
-    struct Table {
-        typename L::fn at[5][3][2] = {};
-        Table()
-        {
-#define VD_X(C, M)                                            \
-    at[C][M][0] = &L::template tg<kFrm + kTb + C, M, 32>;     \
-    at[C][M][1] = &L::template tg<kFrm + kTb + C, M, 16>;
-            VD_TG_PAIRS(VD_X)
-#undef VD_X
-        }
-    };
-    static const Table t;
-    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
-}
-
-// Punctured tail-biting frames (channel ids kFrm + kTb + kPun + format, vd_kernel_tg.h; vd_frames.h): the frame
-// launch with both index maps in its loads, the 9 punctured pairs x {O32, O16}, planned by plan_frames.
-template <class L>
-typename L::fn launcher_punct_tb_frames(int ch, int me, bool o16)
-{
-    struct Table {
-        typename L::fn at[5][3][2] = {};
-        Table()
-        {
-#define VD_X(C, M)                                                   \
-    at[C][M][0] = &L::template tg<kFrm + kTb + kPun + C, M, 32>;     \
-    at[C][M][1] = &L::template tg<kFrm + kTb + kPun + C, M, 16>;
-            VD_PUN_PAIRS(VD_X)
-#undef VD_X
-        }
-    };
-    static const Table t;
-    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;
-}
-
-// int8 frames (channel ids kI8 + the family's id + format, vd_kernel_tg.h; vd_frames.h "int8 frames"): the byte twins
-// of the four frame tables above for HARD, SOFT4 and SOFT8 -- 8 pairs x {O32, O16} for frames and tail-biting frames,
-// the 5 without HARD for the two punctured families: 52 kernels, in four tables of their own, planned by plan_frames.
-#define VD_BYTE_PAIRS(X) X(HARD, B32) X(HARD, B16) X(HARD, F16) VD_BYTE_PUN_PAIRS(X)
+// Frame launches (vd_frames.h; channel ids kFrm + kPun, kTb, kI8, kMix by the family's bits + format, vd_kernel_tg.h):
+// vd_decode_tg only, planned by plan_frames, in one table of their own indexed by the family record.  A row per family
+// that has kernels, each over a pair list x {O32, O16}:
+//   frames, tail-biting frames: all 12 pairs (HARD too: a terminated frame needs no neutral code, a tail-biting one has
+//     no pad and no erasure), 24 kernels each; their punctured twins: the 9 punctured pairs, 18 each;
+//   the int8 twins of the four: HARD, SOFT4 and SOFT8, 8 pairs (16 kernels) unpunctured, the 5 without HARD (10)
+//     punctured;
+//   mixed frames, padded and tail-biting: punctured kernels (pun is set), 18 each for floats and 10 each for int8.
+// 84 + 52 + 56 = 192 kernels; every other combination of the bits (mix without pun) has none and returns null.
 #define VD_BYTE_PUN_PAIRS(X) X(SOFT4, B32) X(SOFT4, B16) X(SOFT4, F16) X(SOFT8, B32) X(SOFT8, B16)
-#define VD_BYTE_TABLE(NAME, PAIRS)                                                           \
-    template <class L>                                                                       \
-    typename L::fn NAME(int ch, int me, bool o16)                                            \
-    {                                                                                        \
-        struct Table {                                                                       \
-            typename L::fn at[3][3][2] = {};                                                 \
-            Table()                                                                          \
-            {                                                                                \
-                PAIRS(VD_X)                                                                  \
-            }                                                                                \
-        };                                                                                   \
-        static const Table t;                                                                \
-        return ch >= 0 && ch < 3 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;         \
-    }
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + C, M, 16>;
-VD_BYTE_TABLE(launcher_byte_frames, VD_BYTE_PAIRS)
-#undef VD_X
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + kPun + C, M, 16>;
-VD_BYTE_TABLE(launcher_byte_punct_frames, VD_BYTE_PUN_PAIRS)
-#undef VD_X
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + kTb + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + kTb + C, M, 16>;
-VD_BYTE_TABLE(launcher_byte_tb_frames, VD_BYTE_PAIRS)
-#undef VD_X
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kI8 + kFrm + kTb + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kI8 + kFrm + kTb + kPun + C, M, 16>;
-VD_BYTE_TABLE(launcher_byte_punct_tb_frames, VD_BYTE_PUN_PAIRS)
-#undef VD_X
-// Mixed frames (channel ids kMix + a punctured frame id, vd_kernel_tg.h; vd_frames.h "mixed frames"): the mixed-rate
-// twins of the two punctured float tables (9 pairs x {O32, O16} each) and of the two punctured byte tables (5 pairs x
-// {O32, O16} each): 56 kernels, in four tables of their own, planned by plan_frames like every frame launch.
-#define VD_MIX_TABLE(NAME, PAIRS)                                                            \
-    template <class L>                                                                       \
-    typename L::fn NAME(int ch, int me, bool o16)                                            \
-    {                                                                                        \
-        struct Table {                                                                       \
-            typename L::fn at[5][3][2] = {};                                                 \
-            Table()                                                                          \
-            {                                                                                \
-                PAIRS(VD_X)                                                                  \
-            }                                                                                \
-        };                                                                                   \
-        static const Table t;                                                                \
-        return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[ch][me][o16] : nullptr;         \
-    }
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kFrm + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kFrm + kPun + C, M, 16>;
-VD_MIX_TABLE(launcher_mixed_frames, VD_PUN_PAIRS)
-#undef VD_X
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kFrm + kTb + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kFrm + kTb + kPun + C, M, 16>;
-VD_MIX_TABLE(launcher_mixed_tb_frames, VD_PUN_PAIRS)
-#undef VD_X
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kI8 + kFrm + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kI8 + kFrm + kPun + C, M, 16>;
-VD_MIX_TABLE(launcher_byte_mixed_frames, VD_BYTE_PUN_PAIRS)
-#undef VD_X
-#define VD_X(C, M) at[C][M][0] = &L::template tg<kMix + kI8 + kFrm + kTb + kPun + C, M, 32>; at[C][M][1] = &L::template tg<kMix + kI8 + kFrm + kTb + kPun + C, M, 16>;
-VD_MIX_TABLE(launcher_byte_mixed_tb_frames, VD_BYTE_PUN_PAIRS)
-#undef VD_X
-#undef VD_MIX_TABLE
-// the mixed-rate kernel of the family (tail-biting or padded) for float (i8 false) or int8 values
+#define VD_BYTE_PAIRS(X) X(HARD, B32) X(HARD, B16) X(HARD, F16) VD_BYTE_PUN_PAIRS(X)
+inline constexpr int frame_family_index(FrameFamily f) { return f.pun + 2 * f.tb + 4 * f.i8 + 8 * f.mix; }
 template <class L>
-typename L::fn launcher_mixed(bool i8, bool tb, int ch, int me, bool o16)
+typename L::fn launcher_frames(FrameFamily f, int ch, int me, bool o16)
 {
-    return i8 ? (tb ? launcher_byte_mixed_tb_frames<L>(ch, me, o16) : launcher_byte_mixed_frames<L>(ch, me, o16))
-              : (tb ? launcher_mixed_tb_frames<L>(ch, me, o16) : launcher_mixed_frames<L>(ch, me, o16));
+    struct Table {
+        typename L::fn at[16][5][3][2] = {};
+        Table()
+        {
+#define VD_X(C, M)                                        \
+    at[fam][C][M][0] = &L::template tg<id + C, M, 32>;    \
+    at[fam][C][M][1] = &L::template tg<id + C, M, 16>;
+#define VD_FAMILY(PUN, TB, I8, MIX, PAIRS)                                                       \
+    {                                                                                            \
+        constexpr int fam = frame_family_index({PUN != 0, TB != 0, I8 != 0, MIX != 0});          \
+        constexpr int id = kFrm + PUN * kPun + TB * kTb + I8 * kI8 + MIX * kMix;                 \
+        PAIRS(VD_X)                                                                              \
+    }
+            VD_FAMILY(0, 0, 0, 0, VD_TG_PAIRS) VD_FAMILY(1, 0, 0, 0, VD_PUN_PAIRS)
+            VD_FAMILY(0, 1, 0, 0, VD_TG_PAIRS) VD_FAMILY(1, 1, 0, 0, VD_PUN_PAIRS)
+            VD_FAMILY(0, 0, 1, 0, VD_BYTE_PAIRS) VD_FAMILY(1, 0, 1, 0, VD_BYTE_PUN_PAIRS)
+            VD_FAMILY(0, 1, 1, 0, VD_BYTE_PAIRS) VD_FAMILY(1, 1, 1, 0, VD_BYTE_PUN_PAIRS)
+            VD_FAMILY(1, 0, 0, 1, VD_PUN_PAIRS) VD_FAMILY(1, 1, 0, 1, VD_PUN_PAIRS)
+            VD_FAMILY(1, 0, 1, 1, VD_BYTE_PUN_PAIRS) VD_FAMILY(1, 1, 1, 1, VD_BYTE_PUN_PAIRS)
+#undef VD_FAMILY
+#undef VD_X
+        }
+    };
+    static const Table t;
+    return ch >= 0 && ch < 5 && me >= 0 && me < 3 ? t.at[frame_family_index(f)][ch][me][o16] : nullptr;
 }
-#undef VD_BYTE_TABLE
-// the byte twin of the family (pun, tb)
-template <class L>
-typename L::fn launcher_byte(bool pun, bool tb, int ch, int me, bool o16)
-{
-    return tb && pun ? launcher_byte_punct_tb_frames<L>(ch, me, o16)
-           : tb      ? launcher_byte_tb_frames<L>(ch, me, o16)
-           : pun     ? launcher_byte_punct_frames<L>(ch, me, o16)
-                     : launcher_byte_frames<L>(ch, me, o16);
-}
+static_assert(kFrameHard == HARD && kFrameSoft8 == SOFT8, "vd_frames.h names the formats its refusals go by");
 
 // ---------------------------------------------------------------- the knobs (read once, at vd_create)
 struct Knobs {
@@ -408,15 +292,12 @@ inline constexpr const char* kCoreNames[3] = {"B32", "B16", "F16"};
 inline std::string plan_name(const LaunchPlan& p, int o, int input)
 {
     if (!p.launches) return "-";
-    const bool mix = input >= 11 && input <= 14;
-    const bool i8 = (input >= 7 && input <= 10) || (mix && input >= 13);
-    if (mix) input = (input & 1) ? 4 : 6;  // the punctured family's name with MIX+ before it
-    else if (i8) input -= 4;               // the float twin's name with I8+ after FRM+
-    const std::string fam = std::string(mix ? "MIX+" : "") + (input == 6 ? "TB+PUN+" : input == 5 ? "TB+" : input == 4 ? "PUN+" : "");
-    const std::string args = std::string(input >= 3 && input <= 6 ? "FRM+" + std::string(i8 ? "I8+" : "") + fam :
-                                         input == 2 ? "PUN+" : input ? "LLR+" : "") +
-                             kChNames[ch_of(o)] + "," + kCoreNames[met_of(o)] + "," + (out_of(o) ? "O16" : "O32") + ">";
-    if (input == 3 || input == 4 || input == 5 || input == 6)
+    const bool frames = input >= 3 && input <= 14;
+    const FrameFamily f = frames ? frame_family_of_input(input) : FrameFamily{};
+    const std::string fam = std::string("FRM+") + (f.i8 ? "I8+" : "") + (f.mix ? "MIX+" : "") + (f.tb ? "TB+" : "") + (f.pun ? "PUN+" : "");
+    const std::string args = (frames ? fam : input == 2 ? "PUN+" : input ? "LLR+" : "") + std::string(kChNames[ch_of(o)]) + "," +
+                             kCoreNames[met_of(o)] + "," + (out_of(o) ? "O16" : "O32") + ">";
+    if (frames)
         return "vd_decode_tg<" + args + " one frame per wave, " + (ch_of(o) == SOFT16 ? "int32 tagged patterns" : "fp32 tagged core") +
                (p.parts > 1 ? ", " + std::to_string(p.parts) + " parts per frame: one part per wave" : "");
     if (p.form == Form::PkBatched) return "vd_decode_pk<" + args + " batched: two chunks per wave, int16 halves";

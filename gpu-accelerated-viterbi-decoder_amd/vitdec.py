@@ -387,6 +387,20 @@ class ViterbiCUDA:
         return v.value
 
     # ---- independent frames, decoded from first bit to last (vd_capi.h "independent frames") ----
+    def _run_frames_host(self, who, nframes, maxFrameBits, frame_bits, call):
+        """What the blocking frame wrappers share: the output array, the lengths as uint32 (one per frame), the timing
+        float and the call, call(out_ptr, row_bytes, frame_bits_ptr, ms_ref) -> status.  Returns (out, ms)."""
+        row = frame_output_size(self.options, maxFrameBits)
+        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
+        fb = None
+        if frame_bits is not None:
+            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
+            if fb.shape != (nframes,):
+                raise VitdecError(f"{who}: frame_bits must hold one length per frame")
+        ms = ctypes.c_float(0.0)
+        _check(call(out.ctypes.data, row, fb.ctypes.data if fb is not None else None, ctypes.byref(ms)))
+        return out, ms.value
+
     def run_frames(self, llr_h, terminated=True, scale=40000.0, frame_bits=None):
         """Blocking decode of nframes frames in one launch.  llr_h: float array [nframes, 2 * maxFrameBits], frame f
         in row f (first encoder output first, encoder started in state 0); frame_bits: the stages of each frame
@@ -399,18 +413,10 @@ class ViterbiCUDA:
         if llr_h.ndim != 2 or llr_h.shape[1] % 2:
             raise VitdecError("run_frames: llr_h must be [nframes, 2 * maxFrameBits]")
         nframes, max_bits = llr_h.shape[0], llr_h.shape[1] // 2
-        row = frame_output_size(self.options, max_bits)
-        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
-        fb = None
-        if frame_bits is not None:
-            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
-            if fb.shape != (nframes,):
-                raise VitdecError("run_frames: frame_bits must hold one length per frame")
-        ms = ctypes.c_float(0.0)
-        _check(lib().vd_run_frames(self._h, llr_h.ctypes.data, 8 * max_bits, out.ctypes.data, row,
-                                   fb.ctypes.data if fb is not None else None, max_bits, nframes, 1 if terminated else 0,
-                                   scale, ctypes.byref(ms)))
-        return out, ms.value
+        return self._run_frames_host(
+            "run_frames", nframes, max_bits, frame_bits, lambda out, row, bits, ms: lib().vd_run_frames(
+                self._h, llr_h.ctypes.data, 8 * max_bits, out, row, bits, max_bits, nframes, 1 if terminated else 0,
+                scale, ms))
 
     def run_device_frames(self, llr_ptr, llr_stride, output_ptr, output_stride, maxFrameBits, nframes, terminated=True,
                           scale=40000.0, frame_bits_ptr=0, stream=0):
@@ -439,18 +445,10 @@ class ViterbiCUDA:
             raise VitdecError(f"run_punct_frames: rows of {rx_h.shape[1]} received values, punctured_len{tuple(pattern)} "
                               f"of {2 * maxFrameBits} is {need}")
         nframes = rx_h.shape[0]
-        row = frame_output_size(self.options, maxFrameBits)
-        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
-        fb = None
-        if frame_bits is not None:
-            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
-            if fb.shape != (nframes,):
-                raise VitdecError("run_punct_frames: frame_bits must hold one length per frame")
-        ms = ctypes.c_float(0.0)
-        _check(lib().vd_run_punct_frames(self._h, rx_h.ctypes.data, 4 * rx_h.shape[1], out.ctypes.data, row,
-                                         fb.ctypes.data if fb is not None else None, maxFrameBits, nframes,
-                                         1 if terminated else 0, scale, *pattern, ctypes.byref(ms)))
-        return out, ms.value
+        return self._run_frames_host(
+            "run_punct_frames", nframes, maxFrameBits, frame_bits, lambda out, row, bits, ms: lib().vd_run_punct_frames(
+                self._h, rx_h.ctypes.data, 4 * rx_h.shape[1], out, row, bits, maxFrameBits, nframes,
+                1 if terminated else 0, scale, *pattern, ms))
 
     def run_device_punct_frames(self, rx_ptr, rx_stride, output_ptr, output_stride, maxFrameBits, nframes, pattern,
                                 terminated=True, scale=40000.0, frame_bits_ptr=0, stream=0):
@@ -475,18 +473,9 @@ class ViterbiCUDA:
         if llr_h.ndim != 2 or llr_h.shape[1] % 2:
             raise VitdecError("run_tb_frames: llr_h must be [nframes, 2 * maxFrameBits]")
         nframes, max_bits = llr_h.shape[0], llr_h.shape[1] // 2
-        row = frame_output_size(self.options, max_bits)
-        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
-        fb = None
-        if frame_bits is not None:
-            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
-            if fb.shape != (nframes,):
-                raise VitdecError("run_tb_frames: frame_bits must hold one length per frame")
-        ms = ctypes.c_float(0.0)
-        _check(lib().vd_run_tb_frames(self._h, llr_h.ctypes.data, 8 * max_bits, out.ctypes.data, row,
-                                      fb.ctypes.data if fb is not None else None, max_bits, nframes, scale,
-                                      ctypes.byref(ms)))
-        return out, ms.value
+        return self._run_frames_host(
+            "run_tb_frames", nframes, max_bits, frame_bits, lambda out, row, bits, ms: lib().vd_run_tb_frames(
+                self._h, llr_h.ctypes.data, 8 * max_bits, out, row, bits, max_bits, nframes, scale, ms))
 
     def run_device_tb_frames(self, llr_ptr, llr_stride, output_ptr, output_stride, maxFrameBits, nframes, scale=40000.0,
                              frame_bits_ptr=0, stream=0):
@@ -513,18 +502,10 @@ class ViterbiCUDA:
             raise VitdecError(f"run_punct_tb_frames: rows of {rx_h.shape[1]} received values, punctured_len{tuple(pattern)} "
                               f"of {2 * maxFrameBits} is {need}")
         nframes = rx_h.shape[0]
-        row = frame_output_size(self.options, maxFrameBits)
-        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
-        fb = None
-        if frame_bits is not None:
-            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
-            if fb.shape != (nframes,):
-                raise VitdecError("run_punct_tb_frames: frame_bits must hold one length per frame")
-        ms = ctypes.c_float(0.0)
-        _check(lib().vd_run_punct_tb_frames(self._h, rx_h.ctypes.data, 4 * rx_h.shape[1], out.ctypes.data, row,
-                                            fb.ctypes.data if fb is not None else None, maxFrameBits, nframes, scale,
-                                            *pattern, ctypes.byref(ms)))
-        return out, ms.value
+        return self._run_frames_host(
+            "run_punct_tb_frames", nframes, maxFrameBits, frame_bits, lambda out, row, bits, ms: lib().vd_run_punct_tb_frames(
+                self._h, rx_h.ctypes.data, 4 * rx_h.shape[1], out, row, bits, maxFrameBits, nframes, scale, *pattern,
+                ms))
 
     def run_device_punct_tb_frames(self, rx_ptr, rx_stride, output_ptr, output_stride, maxFrameBits, nframes, pattern,
                                    scale=40000.0, frame_bits_ptr=0, stream=0):
@@ -558,18 +539,10 @@ class ViterbiCUDA:
             raise VitdecError(f"run_byte_frames: rows of {q_h.shape[1]} values, punctured_len{tuple(pattern)} of "
                               f"{2 * maxFrameBits} is {need}")
         nframes = q_h.shape[0]
-        row = frame_output_size(self.options, maxFrameBits)
-        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
-        fb = None
-        if frame_bits is not None:
-            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
-            if fb.shape != (nframes,):
-                raise VitdecError("run_byte_frames: frame_bits must hold one length per frame")
-        ms = ctypes.c_float(0.0)
-        _check(lib().vd_run_byte_frames(self._h, q_h.ctypes.data, q_h.shape[1], out.ctypes.data, row,
-                                        fb.ctypes.data if fb is not None else None, maxFrameBits, nframes, kind, scale,
-                                        *pattern, ctypes.byref(ms)))
-        return out, ms.value
+        return self._run_frames_host(
+            "run_byte_frames", nframes, maxFrameBits, frame_bits, lambda out, row, bits, ms: lib().vd_run_byte_frames(
+                self._h, q_h.ctypes.data, q_h.shape[1], out, row, bits, maxFrameBits, nframes, kind, scale, *pattern,
+                ms))
 
     def run_device_byte_frames(self, q_ptr, q_stride, output_ptr, output_stride, maxFrameBits, nframes, kind,
                                pattern=(1, 1, 1), scale=1.0, frame_bits_ptr=0, stream=0):
@@ -615,24 +588,17 @@ class ViterbiCUDA:
             if off.ndim != 1 or rx_h.ndim != 1:
                 raise VitdecError(f"{who}: with offsets rx_h is one flat buffer and offsets holds one index per frame")
             nframes, stride, total = off.size, 0, rx_h.size
-        row = frame_output_size(self.options, maxFrameBits)
-        out = np.zeros((nframes, row // np.dtype(self.decPack_t).itemsize), dtype=self.decPack_t)
-        fb = rt = None
-        if frame_bits is not None:
-            fb = np.ascontiguousarray(frame_bits, dtype=np.uint32)
-            if fb.shape != (nframes,):
-                raise VitdecError(f"{who}: frame_bits must hold one length per frame")
-        if rates is not None:
-            rt = np.ascontiguousarray(rates, dtype=np.uint8)
-            if rt.shape != (nframes,):
-                raise VitdecError(f"{who}: rates must hold one pattern index per frame")
-        if rx_h.size == 0:
-            rx_h = np.zeros(4, dtype=dtype)  # (a buffer to point at: no frame reads a value)
-        ms = ctypes.c_float(0.0)
-        _check(fn(self._h, rx_h.ctypes.data, stride, off.ctypes.data if off is not None else None, total, out.ctypes.data, row,
-                  fb.ctypes.data if fb is not None else None, rt.ctypes.data if rt is not None else None, maxFrameBits,
-                  nframes, kind, scale, ctypes.byref(ms)))
-        return out, ms.value
+
+        def call(out, row, bits, ms):  # (the rates are checked after the lengths)
+            rt = None
+            if rates is not None:
+                rt = np.ascontiguousarray(rates, dtype=np.uint8)
+                if rt.shape != (nframes,):
+                    raise VitdecError(f"{who}: rates must hold one pattern index per frame")
+            rx = rx_h if rx_h.size else np.zeros(4, dtype=dtype)  # (a buffer to point at: no frame reads a value)
+            return fn(self._h, rx.ctypes.data, stride, off.ctypes.data if off is not None else None, total, out, row, bits,
+                      rt.ctypes.data if rt is not None else None, maxFrameBits, nframes, kind, scale, ms)
+        return self._run_frames_host(who, nframes, maxFrameBits, frame_bits, call)
 
     def run_mixed_frames(self, rx_h, kind, maxFrameBits, scale=40000.0, frame_bits=None, rates=None, offsets=None):
         """Blocking decode of nframes frames at mixed code rates in one launch.  Frame f decodes under pattern rates[f]

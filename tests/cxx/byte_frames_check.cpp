@@ -11,7 +11,7 @@
 //   value of the frame; there it equals the enumeration's index (unpunctured: 2 x the frame stage), and the float
 //   helper's offset is 4 x it; outside, offset + access does not wrap in 32 bits and the float helper's offset is
 //   outside its range too.
-// Also: byte_frame_args_error message by message, the 52 kernels of the four tables and the names of llr 7 .. 10.
+// Also: frame_args_error message by message for the int8 families, the 52 kernels of the four tables and the names of llr 7 .. 10.
 // Arguments (tests/test_byte_frames.py passes the lists of tests/ptb_common.py): sizes=S,S,... parts=b,b,...
 // pat=period,keep0,keep1 (repeated).  Built with hipcc and the host sanitizers; prints "ok" or the first mismatch.
 #include <algorithm>
@@ -25,6 +25,7 @@
 #include <vector>
 #include "vd_kernel_tg.h"
 #include "vd_plan.h"
+#include "frame_args.h"
 
 using namespace vd;
 
@@ -91,8 +92,8 @@ static int check_frame(const Pat& p, uint32_t S, uint32_t partBits)
     Enum en;
     en.build(p, S);
     const uint64_t range = en.kept, frange = 4ull * en.kept;  // bytes of the int8 frame, of the float frame
-    if (byte_pfrm_bytes(pn, S) != range || range != punct_len(pn, 2ull * S) || pfrm_bytes(pn, S) != frange)
-        FAIL("(%d,0x%x,0x%x) S %u: byte_pfrm_bytes %u, enumeration %llu", p.period, p.k0, p.k1, S, byte_pfrm_bytes(pn, S),
+    if (pfrm_bytes<1>(pn, S) != range || range != punct_len(pn, 2ull * S) || pfrm_bytes(pn, S) != frange)
+        FAIL("(%d,0x%x,0x%x) S %u: pfrm_bytes<1> %u, enumeration %llu", p.period, p.k0, p.k1, S, pfrm_bytes<1>(pn, S),
              (unsigned long long)range);
     const uint32_t W = frame_words(S), P = frame_padded_stages(S), Wp = frame_part_words(partBits);
     const uint32_t limit = P + 96;
@@ -115,26 +116,26 @@ static int check_frame(const Pat& p, uint32_t S, uint32_t partBits)
             // the scalar values of the group, as the kernel forms them (punctured frames)
             const PfrmGroup pg = pfrm_group(g0);
             uint32_t r0b, r0f;
-            const uint32_t base1 = byte_pfrm_base(pn, pg.t0, &r0b), base4 = pfrm_base(pn, pg.t0, &r0f);
+            const uint32_t base1 = pfrm_base<1>(pn, pg.t0, &r0b), base4 = pfrm_base(pn, pg.t0, &r0f);
             if (base4 != 4 * base1 || r0b != r0f) FAIL("S %u group %u: base %u vs %u", S, g0, base1, base4);
             for (uint32_t s = 0; s < 96; s++) {
                 const uint32_t q = g0 + s;
                 const bool in_frame = q >= 26 && q - 26 < S;
                 if (plain) {
                     // frames: one 16-bit access per stage against 2 S bytes
-                    const uint32_t o = byte_frame_offset(q), of = frame_offset(q);
+                    const uint32_t o = frame_offset<1>(q), of = frame_offset(q);
                     if (wraps(o, 2)) FAIL("frames S %u stage %u: offset 0x%x wraps", S, q, o);
                     if (inside(o, 2, 2ull * S) != in_frame || inside(of, 8, 8ull * S) != in_frame)
                         FAIL("frames S %u stage %u: offsets 0x%x / 0x%x, in frame %d", S, q, o, of, (int)in_frame);
                     if (in_frame && (o != 2 * (q - 26) || of != 4 * o)) FAIL("frames S %u stage %u: offset %u (float %u)", S, q, o, of);
                     // tail-biting frames: every stage is a frame stage
-                    const uint32_t ot = byte_tb_stage_offset(g0, s, S, rc), otf = tb_stage_offset(g0, s, S, rc);
-                    if (ot != 2 * ext[q] || otf != 4 * ot || !inside(ot, 2, 2ull * S) || byte_tb_offset(ext[q]) != ot)
+                    const uint32_t ot = tb_stage_offset<1>(g0, s, S, rc), otf = tb_stage_offset(g0, s, S, rc);
+                    if (ot != 2 * ext[q] || otf != 4 * ot || !inside(ot, 2, 2ull * S) || tb_offset<1>(ext[q]) != ot)
                         FAIL("tail-biting S %u stage %u (frame stage %u): offset %u (float %u)", S, q, ext[q], ot, otf);
                 }
                 // punctured frames and punctured tail-biting frames: one 8-bit access per value
-                const PfrmOff ob = byte_pfrm_offsets(pn, base1, r0b, pg.lead, s), of = pfrm_offsets(pn, base4, r0f, pg.lead, s);
-                const PfrmOff tb = byte_ptb_stage_offsets(pn, g0, s, S, rc), tf = ptb_stage_offsets(pn, g0, s, S, rc);
+                const PfrmOff ob = pfrm_offsets<1>(pn, base1, r0b, pg.lead, s), of = pfrm_offsets(pn, base4, r0f, pg.lead, s);
+                const PfrmOff tb = ptb_stage_offsets<1>(pn, g0, s, S, rc), tf = ptb_stage_offsets(pn, g0, s, S, rc);
                 const uint32_t pb[2] = {ob.o0, ob.o1}, pf[2] = {of.o0, of.o1}, xb[2] = {tb.o0, tb.o1}, xf[2] = {tf.o0, tf.o1};
                 for (int c = 0; c < 2; c++) {
                     const int32_t want = in_frame ? en.idx[2 * (size_t)(q - 26) + c] : -1;
@@ -222,7 +223,8 @@ static int check_args()
     };
     int i = 0;
     for (const A& a : cases) {
-        const char* why = byte_frame_args_error(a.addr, a.istr, a.ostr, a.maxb, a.nf, a.kind, a.scale, a.period, a.k0, a.k1, a.part);
+        const char* why = check({!byte_frames_unpunctured(a.period, a.k0, a.k1), a.kind == kByteFramesTailbiting, true, false}, a.addr, a.istr, a.ostr,
+                                a.maxb, a.nf, a.kind, a.scale, a.period, a.k0, a.k1, a.part);
         if (a.why ? !why || !strstr(why, a.why) : why != nullptr)
             FAIL("argument case %d: %s, want %s", i, why ? why : "accepted", a.why ? a.why : "accepted");
         i++;
@@ -240,11 +242,10 @@ static int check_table()
                 for (int fam = 0; fam < 4; fam++) {
                     const bool pun = fam & 1, tb = fam & 2;
                     const bool want = ch >= (pun ? 1 : 0) && ch <= 2 && me >= 0 && me < 3 && has_kernel(Form::Tg, ch, me);
-                    const bool got = launcher_byte<Stub>(pun, tb, ch, me, o16 != 0) != nullptr;
+                    const bool got = launcher_frames<Stub>({pun, tb, true, false}, ch, me, o16 != 0) != nullptr;
                     if (got != want) FAIL("table family %d: %d %d %d", fam, ch, me, o16);
                     // ... and the float twin exists wherever the byte one does
-                    const bool twin = (tb && pun ? launcher_punct_tb_frames<Stub>(ch, me, o16 != 0) : tb ? launcher_tb_frames<Stub>(ch, me, o16 != 0) :
-                                       pun ? launcher_punct_frames<Stub>(ch, me, o16 != 0) : launcher_frames<Stub>(ch, me, o16 != 0)) != nullptr;
+                    const bool twin = launcher_frames<Stub>({pun, tb, false, false}, ch, me, o16 != 0) != nullptr;
                     if (got && !twin) FAIL("table family %d: %d %d %d has no float twin", fam, ch, me, o16);
                     n[fam] += got;
                 }

@@ -13,6 +13,7 @@
 #include <vector>
 #include "vd_kernel_tg.h"
 #include "vd_plan.h"
+#include "frame_args.h"
 
 using namespace vd;
 
@@ -116,7 +117,7 @@ static int check_args()
     };
     int i = 0;
     for (const A& a : cases) {
-        const char* why = frame_args_error(a.addr, a.istr, a.ostr, a.maxb, a.nf, a.scale);
+        const char* why = check({false, false, false, false}, a.addr, a.istr, a.ostr, a.maxb, a.nf, kByteFramesTerminated, a.scale);
         if ((why == nullptr) != a.ok) { printf("FAIL argument case %d: %s\n", i, why ? why : "accepted"); return 1; }
         i++;
     }
@@ -143,7 +144,7 @@ static int check_plan()
         for (int me = -1; me <= 3; me++)
             for (int o16 = 0; o16 < 2; o16++) {
                 const bool want = ch >= 0 && ch < 5 && me >= 0 && me < 3 && has_kernel(Form::Tg, ch, me);
-                if ((launcher_frames<Stub>(ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
+                if ((launcher_frames<Stub>({false, false, false, false}, ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
                 n += want;
             }
     if (n != 24) { printf("FAIL %d frame kernels\n", n); return 1; }

@@ -6,7 +6,7 @@
 //     two dwords 0;
 //   mix_max_bytes: for every table and every length, the largest number of kept values of a frame, counted by walking
 //     the frame's 2 S mother positions once per pattern, times the bytes of a value;
-//   mixed_table_error and mixed_args_error message by message;
+//   mixed_table_error and frame_args_error (the mixed families) message by message;
 //   the 56 kernels of the four tables -- one wherever the punctured twin has one -- and the names of llr 11 .. 14.
 // Arguments (tests/test_mixed_frames.py passes its lists): sizes=S,S,... pat=period,keep0,keep1 (repeated; the table
 // is every prefix of them).  Built with hipcc and the host sanitizers; prints "ok" or the first mismatch.
@@ -20,6 +20,7 @@
 #include <vector>
 #include "vd_kernel_tg.h"
 #include "vd_plan.h"
+#include "frame_args.h"
 
 using namespace vd;
 
@@ -182,7 +183,12 @@ static int check_args()
     };
     int i = 0;
     for (const A& a : cases) {
-        const char* why = mixed_args_error(a.addr, a.istr, a.off, a.ostr, a.maxb, a.nf, a.kind, a.scale, a.tab, a.n, a.vb, a.part);
+        FrameArgs c = call_of({true, a.kind == kByteFramesTailbiting, a.vb == 1, true}, a.addr, a.istr, a.ostr, a.maxb, a.nf, a.kind, a.scale);
+        c.offsets = a.off;
+        c.table = a.tab;
+        c.tableN = a.n;
+        c.partBits = a.part;
+        const char* why = why_of(c);
         if (a.why ? !why || !strstr(why, a.why) : why != nullptr)
             FAIL("argument case %d: %s, want %s", i, why ? why : "accepted", a.why ? a.why : "accepted");
         i++;
@@ -203,9 +209,9 @@ static int check_table()
             for (int o16 = 0; o16 < 2; o16++)
                 for (int fam = 0; fam < 4; fam++) {
                     const bool i8 = fam & 1, tb = fam & 2;
-                    const bool got = launcher_mixed<Stub>(i8, tb, ch, me, o16 != 0) != nullptr;
-                    const bool twin = (i8 ? launcher_byte<Stub>(true, tb, ch, me, o16 != 0)
-                                       : tb ? launcher_punct_tb_frames<Stub>(ch, me, o16 != 0) : launcher_punct_frames<Stub>(ch, me, o16 != 0)) != nullptr;
+                    const bool got = launcher_frames<Stub>({true, tb, i8, true}, ch, me, o16 != 0) != nullptr;
+                    const bool twin = launcher_frames<Stub>({true, tb, i8, false}, ch, me, o16 != 0) != nullptr;
+                    if (launcher_frames<Stub>({false, tb, i8, true}, ch, me, o16 != 0)) FAIL("a mixed kernel that is not a punctured one: %d %d %d", ch, me, o16);
                     const bool want = ch >= 1 && ch <= (i8 ? 2 : 4) && me >= 0 && me < 3 && has_kernel(Form::Tg, ch, me);
                     if (got != want || got != twin) FAIL("table family %d: %d %d %d", fam, ch, me, o16);
                     n[fam] += got;

@@ -1,5 +1,5 @@
 // Host check of the launch plan (vd_plan.h): form, grid, tail workgroups, segment table, stats and packNum of
-// plan_launch, the knobs read from the environment, the names of plan_name, and the kernel table, against
+// plan_launch, the knobs read from the environment, the names of plan_name, the kernel table and the frame table, against
 // values worked out by hand from the rules (never from plan_launch itself).  nsimd = 1024 (256 CUs) unless a
 // case says otherwise; the segment tables' workgroup counts come from vd_segplan.h.
 // Built with hipcc on the host by tests/test_plan.py; prints "ok" or the first mismatch.
@@ -150,6 +150,37 @@ int main()
     if (count[0] != 48 || count[1] != 44 || count[2] != 44) {
         printf("FAIL kernel table: %d tg, %d + %d pk launchers\n", count[0], count[1], count[2]);
         return 1;
+    }
+    // the frame table (launcher_frames): 84 float, 52 int8 and 56 mixed kernels, and for every valid option and input code 3 .. 14 a kernel
+    // exactly where vd_decoder_kernel_name names one -- not for punctured frames (4, 6) on HARD, for the int8 twins
+    // (7 .. 10) on HARD, SOFT4 and SOFT8 only and the punctured ones (8, 10) not on HARD, for mixed frames (11 .. 14) not
+    // on HARD and their int8 twins (13, 14) on SOFT4 and SOFT8 only
+    int nframe = 0;
+    for (int fam = 0; fam < 16; fam++)
+        for (int ch = 0; ch < 5; ch++)
+            for (int me = 0; me < 3; me++)
+                for (int o16 = 0; o16 < 2; o16++)
+                    nframe += launcher_frames<Stub>({(fam & 1) != 0, (fam & 2) != 0, (fam & 4) != 0, (fam & 8) != 0}, ch, me, o16 != 0) != nullptr;
+    if (nframe != 84 + 52 + 56) { printf("FAIL frame table: %d kernels\n", nframe); return 1; }
+    for (int o = 0; o < 0x10000; o++) {
+        if (!valid(o)) continue;
+        const int ch = ch_of(o);
+        for (int llr = 3; llr <= 14; llr++) {
+            bool none = false;
+            if ((llr == 4 || llr == 6) && ch == HARD) none = true;
+            if (llr >= 7 && llr <= 10 && (ch > SOFT8 || (ch == HARD && (llr == 8 || llr == 10)))) none = true;
+            if (llr >= 11 && llr <= 14 && (ch == HARD || (llr >= 13 && ch > SOFT8))) none = true;
+            const FrameFamily f = frame_family_of_input(llr);
+            if ((launcher_frames<Stub>(f, ch, met_of(o), out_of(o) == 1) == nullptr) != none) {
+                printf("FAIL frame table: option 0x%x input %d: kernel %s\n", o, llr, none ? "present" : "missing");
+                return 1;
+            }
+            if (f.i8 != ((llr >= 7 && llr <= 10) || llr >= 13) || f.mix != (llr >= 11) || f.tb != (llr == 5 || llr == 6 || llr == 9 || llr == 10 || llr == 12 || llr == 14) ||
+                f.pun != (llr == 4 || llr == 6 || llr == 8 || llr == 10 || llr >= 11)) {
+                printf("FAIL family of input %d\n", llr);
+                return 1;
+            }
+        }
     }
     printf("ok\n");
     return 0;

@@ -1,5 +1,5 @@
 // Host check of the punctured tail-biting frame geometry (vd_frames.h "punctured tail-biting frames"), its argument
-// checks and the kernel table of launcher_punct_tb_frames (vd_plan.h) against a plain enumeration (never against the
+// checks and the kernel table of launcher_frames (vd_plan.h; pun + tb) against a plain enumeration (never against the
 // header's own closed forms).  For a pattern and a frame of S stages the enumeration walks the frame's 2 S mother
 // positions once, counting the kept ones: that gives every kept value's index in the frame's buffer and the
 // buffer's length.  The extended stream is walked by stepping: stage 26 is frame stage 0, stage 0 is found by
@@ -9,7 +9,7 @@
 //   a kept value of the frame stage lies inside the range of pfrm_bytes, at 4 x its index;
 //   a punctured value lies at or above 2^31 with no 32-bit wrap of offset + 4: past any range a frame can have.
 // Also: the form of every group (inside exactly when no lane leaves the unwrapped line, several turns exactly for
-// a wrapping group of a frame under 96 stages), pfrm_bytes against the enumeration's length, ptb_args_error case
+// a wrapping group of a frame under 96 stages), pfrm_bytes against the enumeration's length, frame_args_error case
 // by case, the kernel name and the kernel table.
 // Patterns: 1/2, 2/3, 3/4, (7, 0b1010001, 0b0101111), (16, 0xA5C3, 0x5A3D), (16, 0x8000, 0).  Lengths: every S in
 // 1 .. 400, and 4095, 4096, 4097, 2^20 - 1, 2^20.
@@ -22,6 +22,7 @@
 #include <vector>
 #include "vd_kernel_tg.h"
 #include "vd_plan.h"
+#include "frame_args.h"
 
 using namespace vd;
 
@@ -154,7 +155,7 @@ static int check_args()
     };
     int i = 0;
     for (const A& a : cases) {
-        const char* why = ptb_args_error(a.addr, a.istr, a.ostr, a.maxb, a.nf, a.scale, a.period, a.k0, a.k1);
+        const char* why = check({true, true, false, false}, a.addr, a.istr, a.ostr, a.maxb, a.nf, kByteFramesTailbiting, a.scale, a.period, a.k0, a.k1);
         if ((why == nullptr) != a.ok) { printf("FAIL argument case %d: %s\n", i, why ? why : "accepted"); return 1; }
         i++;
     }
@@ -169,13 +170,13 @@ static int check_table()
         for (int me = -1; me <= 3; me++)
             for (int o16 = 0; o16 < 2; o16++) {
                 const bool want = ch >= 1 && ch < 5 && me >= 0 && me < 3 && has_kernel(Form::Tg, ch, me);
-                if ((launcher_punct_tb_frames<Stub>(ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
-                if (want != (launcher_punct_frames<Stub>(ch, me, o16 != 0) != nullptr)) { printf("FAIL table vs FRM+PUN %d %d %d\n", ch, me, o16); return 1; }
+                if ((launcher_frames<Stub>({true, true, false, false}, ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
+                if (want != (launcher_frames<Stub>({true, false, false, false}, ch, me, o16 != 0) != nullptr)) { printf("FAIL table vs FRM+PUN %d %d %d\n", ch, me, o16); return 1; }
                 n += want;
             }
     if (n != 18) { printf("FAIL %d punctured tail-biting frame kernels\n", n); return 1; }
     for (int me = 0; me < 3; me++)
-        if (launcher_punct_tb_frames<Stub>(HARD, me, false) || launcher_punct_tb_frames<Stub>(HARD, me, true)) { printf("FAIL HARD kernel\n"); return 1; }
+        if (launcher_frames<Stub>({true, true, false, false}, HARD, me, false) || launcher_frames<Stub>({true, true, false, false}, HARD, me, true)) { printf("FAIL HARD kernel\n"); return 1; }
     const std::string nm = plan_name(plan_frames(0x012, 5), 0x012, 6);
     if (nm.rfind("vd_decode_tg<FRM+TB+PUN+SOFT8,B16,O32> one frame per wave, ", 0) != 0) { printf("FAIL name %s\n", nm.c_str()); return 1; }
     if (plan_name(plan_frames(0x103, 7), 0x103, 6).rfind("vd_decode_tg<FRM+TB+PUN+SOFT16,B32,O16>", 0) != 0) { printf("FAIL name\n"); return 1; }

@@ -1,5 +1,5 @@
 // Host check of the punctured-frame helpers (vd_frames.h "punctured frames") and the kernel table of
-// launcher_punct_frames (vd_plan.h) against a plain enumeration of the padded, depunctured stream (never against
+// launcher_frames (vd_plan.h; pun) against a plain enumeration of the padded, depunctured stream (never against
 // the headers' own closed forms).  For a pattern and a frame of S stages the enumeration walks the frame's 2 S
 // mother positions once, counting the kept ones: that gives every kept value's index in the frame's buffer and
 // the buffer's length.  Then, for every group start the decode of the frame reaches (the group after the last
@@ -30,6 +30,7 @@
 #include <vector>
 #include "vd_kernel_tg.h"
 #include "vd_plan.h"
+#include "frame_args.h"
 
 using namespace vd;
 
@@ -238,7 +239,7 @@ static int check_args()
     };
     int i = 0;
     for (const A& a : cases) {
-        const char* why = pfrm_args_error(a.addr, a.istr, a.ostr, a.maxb, a.nf, a.scale, a.period, a.k0, a.k1);
+        const char* why = check({true, false, false, false}, a.addr, a.istr, a.ostr, a.maxb, a.nf, kByteFramesTerminated, a.scale, a.period, a.k0, a.k1);
         if ((why == nullptr) != a.ok) { printf("FAIL argument case %d: %s\n", i, why ? why : "accepted"); return 1; }
         i++;
     }
@@ -253,13 +254,13 @@ static int check_table()
         for (int me = -1; me <= 3; me++)
             for (int o16 = 0; o16 < 2; o16++) {
                 const bool want = ch >= 1 && ch < 5 && me >= 0 && me < 3 && has_kernel(Form::Tg, ch, me);
-                if ((launcher_punct_frames<Stub>(ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
+                if ((launcher_frames<Stub>({true, false, false, false}, ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
                 if (want != (launcher_punct<Stub>(ch, me, o16 != 0) != nullptr)) { printf("FAIL table vs PUN %d %d %d\n", ch, me, o16); return 1; }
                 n += want;
             }
     if (n != 18) { printf("FAIL %d punctured frame kernels\n", n); return 1; }
     for (int me = 0; me < 3; me++)
-        if (launcher_punct_frames<Stub>(HARD, me, false) || launcher_punct_frames<Stub>(HARD, me, true)) { printf("FAIL HARD kernel\n"); return 1; }
+        if (launcher_frames<Stub>({true, false, false, false}, HARD, me, false) || launcher_frames<Stub>({true, false, false, false}, HARD, me, true)) { printf("FAIL HARD kernel\n"); return 1; }
     const std::string nm = plan_name(plan_frames(0x012, 5), 0x012, 4);
     if (nm.rfind("vd_decode_tg<FRM+PUN+SOFT8,B16,O32> one frame per wave, ", 0) != 0) { printf("FAIL name %s\n", nm.c_str()); return 1; }
     if (plan_name(plan_frames(0x103, 7), 0x103, 4).rfind("vd_decode_tg<FRM+PUN+SOFT16,B32,O16>", 0) != 0) { printf("FAIL name\n"); return 1; }

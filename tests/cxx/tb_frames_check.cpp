@@ -5,7 +5,7 @@
 // lies inside the frame's 8 S bytes, the uniform "this group wraps" predicate says exactly whether some lane leaves
 // the unwrapped line 8 (p - 26), the scalar first-stage residue and the lane reduction agree with the stepping; the
 // reciprocals' bounds as stated; the argument checks; the grids of plan_frames, the kernel name and the kernel
-// table of launcher_tb_frames.
+// table of launcher_frames (the tail-biting family).
 // Built with hipcc and the host sanitizers by tests/test_tb_frames.py; prints "ok" or the first mismatch.
 #include <cmath>
 #include <cstdint>
@@ -14,6 +14,7 @@
 #include <string>
 #include "vd_kernel_tg.h"
 #include "vd_plan.h"
+#include "frame_args.h"
 
 using namespace vd;
 
@@ -126,7 +127,7 @@ static int check_args()
     };
     int i = 0;
     for (const A& a : cases) {
-        const char* why = tb_args_error(a.addr, a.istr, a.ostr, a.maxb, a.nf, a.scale);
+        const char* why = check({false, true, false, false}, a.addr, a.istr, a.ostr, a.maxb, a.nf, kByteFramesTailbiting, a.scale);
         if ((why == nullptr) != a.ok) { printf("FAIL argument case %d: %s\n", i, why ? why : "accepted"); return 1; }
         i++;
     }
@@ -156,7 +157,7 @@ static int check_plan()
         for (int me = -1; me <= 3; me++)
             for (int o16 = 0; o16 < 2; o16++) {
                 const bool want = ch >= 0 && ch < 5 && me >= 0 && me < 3 && has_kernel(Form::Tg, ch, me);
-                if ((launcher_tb_frames<Stub>(ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
+                if ((launcher_frames<Stub>({false, true, false, false}, ch, me, o16 != 0) != nullptr) != want) { printf("FAIL table %d %d %d\n", ch, me, o16); return 1; }
                 n += want;
             }
     if (n != 24) { printf("FAIL %d tail-biting frame kernels\n", n); return 1; }

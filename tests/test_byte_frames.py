@@ -1,4 +1,4 @@
-"""int8 frames on the CPU: the byte geometry of the four frame families, byte_frame_args_error message by message, the
+"""int8 frames on the CPU: the byte geometry of the four frame families, frame_args_error message by message for the int8 families, the
 52 kernels of the byte twins' tables and their names (csrc/vd_frames.h "int8 frames", vd_plan.h; checked by
 tests/cxx/byte_frames_check.cpp against a plain enumeration, built stand-alone with the host sanitizers), and the
 binding's declarations.  The decodes on the GPU: tests/test_gpu_byte_frames.py."""

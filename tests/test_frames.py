@@ -19,10 +19,9 @@ def name(o):
     return f"0x{o:03x}"
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_geometry_arguments_and_plan_against_enumeration(tmp_path):
-    exe = tmp_path / "frames_check"
-    src = os.path.join(ROOT, "tests", "cxx", "frames_check.cpp")
+def check_program(tmp_path, name):
+    exe = tmp_path / name
+    src = os.path.join(ROOT, "tests", "cxx", name + ".cpp")
     csrc = os.path.join(ROOT, "gpu-accelerated-viterbi-decoder_amd", "csrc")
     r = subprocess.run([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O1", "-std=c++17", "-w", "-Xarch_host",
                         "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-I", csrc, src,
@@ -30,6 +29,17 @@ def test_geometry_arguments_and_plan_against_enumeration(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip() == "ok", (r.stdout[-2000:], r.stderr[-2000:])
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_geometry_arguments_and_plan_against_enumeration(tmp_path):
+    check_program(tmp_path, "frames_check")
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_argument_check_precedence_of_every_family(tmp_path):
+    """which error wins when several apply, by status code and message (tests/cxx/frame_args_check.cpp)"""
+    check_program(tmp_path, "frame_args_check")
 
 
 def test_numpy_encoder_is_the_harness_encoder(vo):

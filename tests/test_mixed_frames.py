@@ -1,5 +1,5 @@
 """Mixed frames on the CPU: the pattern table's records, the largest received length over a table, mixed_table_error and
-mixed_args_error message by message, the 56 kernels of the mixed launches' tables and their names (csrc/vd_frames.h
+frame_args_error message by message for the mixed families, the 56 kernels of the mixed launches' tables and their names (csrc/vd_frames.h
 "mixed frames", vd_plan.h; checked by tests/cxx/mixed_frames_check.cpp against a plain enumeration, built stand-alone with
 the host sanitizers), vitdec.mixed_layout against the binding's own puncturer, and the header, the exports and the
 binding's declarations.  The decodes on the GPU: tests/test_gpu_mixed_frames.py."""
